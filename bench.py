@@ -11,6 +11,12 @@ Workload = BASELINE.json configs[1]: audio-only G + PatchGAN D, 256x256 mel,
 batch 16 per GPU; fp32 tensors, conv products on the 16-bit matrix cores through the
 f16x2 / bf16x3 operand splits with fp32 accumulation (the `config.math` string of the
 JSON line is generated from the switches in effect).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds
+everything else the benchmark measures: the roofline / whole-step floor passes, the
+front-end stages, the launch modes, the bounded legs on the other configs (`extra`),
+the CPU baseline and, at N > 1, the exposed communication time.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -159,6 +165,8 @@ def compact_line(full):
 def emit(full, args):
     """write the whole record to the detail file (never to stdout / stderr: the driver keeps only a tail) and print the contract line LAST"""
     path = args.detail
+    if path is None and not args.full:
+        path = ""                                       # a plain run writes no detail file unless --detail names one
     if path is None:
         d = os.path.join(ROOT, "gpurun_out")
         try:
@@ -175,6 +183,34 @@ def emit(full, args):
             pass
     sys.stderr.flush()
     print(compact_line(full), flush=True)
+
+
+DUMP_LIMIT = 64_000_000           # bytes: all the files of one --dump-outputs together
+DUMP_BIG = 8_000_000              # bytes: an array above this is sampled when the whole set would not fit DUMP_LIMIT
+DUMP_SAMPLE = 2_000_000           # elements kept of a sampled array
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy, float64 kept as float64, everything else as float32.  When the whole set would pass
+    DUMP_LIMIT, every array above DUMP_BIG is replaced by DUMP_SAMPLE of its (flattened) elements at indices drawn from a fixed seed, in
+    ascending order: the same arguments give the same files, so two builds can be compared output for output."""
+    import numpy as np
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    sample = sum(a.nbytes for a in host.values()) > DUMP_LIMIT
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in host.items():
+        if sample and a.nbytes > DUMP_BIG:
+            idx = np.sort(np.random.default_rng(1234).choice(a.size, size=DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, (name, total)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def parse():
@@ -201,6 +237,11 @@ def parse():
     ap.add_argument("--cpu-batch", type=int, default=2, help="clips per CPU-baseline step (bounded sample)")
     ap.add_argument("--share-gpu", action="store_true", help="--gpus N on a box with fewer than N devices: the ranks share the visible device(s) and "
                     "exchange over gloo (RCCL refuses two ranks on one device).  Exercises the launch contract and the bucketed exchange; not a measurement")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run everything else the benchmark measures: roofline and "
+                    "whole-step floor passes, front-end stages, launch modes, the `extra` legs, the CPU baseline, comm_ms_exposed at N > 1 "
+                    "(the --no-* switches and --layers act within it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB in all; a larger array is replaced by a fixed seeded sample of its elements)")
     a = ap.parse_args()
     wn = a.config == "wavenet"
     a.steps = a.steps if a.steps is not None else (2048 if wn else 30)
@@ -667,8 +708,10 @@ def main_wavenet(args):
     net = WaveNet(dropout=0.0).to(dev).eval()
     c = torch.rand(B, 80, T // hop, device=dev)
     timing = {"warmup": T - args.steps}
-    net.incremental_forward(None, c=c, T=T, log_scale_min=-7.0, timing=timing)
+    wav = net.incremental_forward(None, c=c, T=T, log_scale_min=-7.0, timing=timing)
     ms = timing["ms"] / timing["steps"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"samples": wav})                 # (B, 1, T): the synthesised streams, warm-up steps included
     n_param = sum(p.numel() for p in net.parameters())
     fused = os.environ.get("VIAI_WN_FUSED", "1") != "0"
     pipe = timing.get("form") == "pipe"           # round 6: one persistent launch, the 27 stages own compute units and work on different streams (csrc/wavenet_pipe.hip)
@@ -716,7 +759,7 @@ def main_wavenet(args):
                 if "wn_pipe" in k and "hbm_bytes_per_time_step" in v:
                     out["roofline"]["traffic"] = round(v["hbm_bytes_per_time_step"])
                     out["roofline"]["traffic_source"] = "committed: profiles/%s (rocprofv3 --pmc, 2*FETCH_SIZE+WRITE_SIZE per time step)" % os.path.basename(pm[-1])
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import wavenet_oracle as W
         try:
             avail = len(os.sched_getaffinity(0))
@@ -742,9 +785,9 @@ def extra_legs(budget_s=170.0):
     configs[2] (vision-infused, 3 steps + a one-clip CPU step), configs[4] (WaveNet synthesis, 2048 time steps + 256 CPU time steps), configs[1] under
     VIAI_MATH=fp32 (5 steps).  Each child prints its own contract line and writes its own detail file; the parent quotes a few numbers of each
     (compact_leg).  The legs share one wall-time budget: a leg that would start after it is skipped and says so."""
-    legs = {"av": (["--config", "av", "--steps", "3", "--warmup", "1"], {}),
-            "wavenet": (["--config", "wavenet", "--steps", "2048", "--warmup", "64"], {}),
-            "audio_exact_fp32": (["--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extra"], {"VIAI_MATH": "fp32"})}
+    legs = {"av": (["--full", "--config", "av", "--steps", "3", "--warmup", "1"], {}),
+            "wavenet": (["--full", "--config", "wavenet", "--steps", "2048", "--warmup", "64"], {}),
+            "audio_exact_fp32": (["--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extra"], {"VIAI_MATH": "fp32"})}
     res = {}
     t_all = time.perf_counter()
     for tag, (argv, envx) in legs.items():
@@ -839,8 +882,11 @@ def main():
     ms_per_step = elapsed_ms / args.steps
     value = world * args.batch * args.steps / (elapsed_ms * 1e-3)
     losses = model.get_loss_items()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"fake": model.fake, "losses": torch.tensor(losses, dtype=torch.float64),
+                                         "params_G": model.arena_G.flat, "params_D": model.arena_D.flat})
     comm_exposed = None
-    if world > 1:
+    if world > 1 and args.full:
         # the same K steps without the collectives (replicas diverge from here on; nothing is measured afterwards):
         # what the exchange adds to the step after overlapping it with the backward / the next step's D(real) branch
         model._skip_exchange = True
@@ -883,7 +929,7 @@ def main():
                                      "Adam(E,G) + weight re-pack overlap the next step's D(real) forward/backward; comm_ms_exposed = ms_per_step - "
                                      "ms_per_step of the same steps without the collectives" % ("gloo (host-staged)" if shared else "RCCL"))
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # instrumented eager pass over the same workload: HIP events around every conv launch
         m2 = AudioModel(hp, device=dev, use_graph=False)
         m2._skip_exchange = True              # rank 0 only: the other ranks are already at the final barrier, a collective here would hang
@@ -1011,20 +1057,20 @@ def main():
                                             "dominant_kernel": next((v["mfma_busy"] for k, v in ps["kernels"].items() if PMC_KERNEL_OF.get(dom, "?").replace(" ", "") in k.replace(" ", "")), None),
                                             "source": "committed: profiles/%s (tools/pmc_step.sh, not measured in this run)" % os.path.basename(steps_pmc[-1])}
         del m2
-    if rank == 0 and world == 1 and not av and not args.no_roofline:            # (N = 1 only: at N > 1 the other ranks wait in the final barrier)
+    if rank == 0 and world == 1 and not av and args.full and not args.no_roofline:            # (N = 1 only: at N > 1 the other ranks wait in the final barrier)
         out["stages"] = front_end_stages(dev, args.batch, args.bins, args.frames)
-    if rank == 0 and world == 1 and not av and not args.no_roofline:
+    if rank == 0 and world == 1 and not av and args.full and not args.no_roofline:
         out["config"]["launch_modes"] = launch_modes(hp, dev, s, mask)
         out["config"]["host_enqueue_note"] = ("host_enqueue_ms_per_step is the LOOP figure: the host runs ahead until the device queues fill and then "
                                               "waits inside a launch, so it tracks the device time in every launch mode; the host's own cost per step is "
                                               "launch_modes.*.host_ms_per_step_idle_queue (one step enqueued into an idle queue): eager vs the C launch "
                                               "plan (bench.py --plan; bitwise the eager step)")
-    if rank == 0 and world == 1 and not av and not args.no_roofline and not args.no_extra and (args.batch, args.bins, args.frames) == (16, 256, 256):
+    if rank == 0 and world == 1 and not av and args.full and not args.no_roofline and not args.no_extra and (args.batch, args.bins, args.frames) == (16, 256, 256):
         del model
         model = None
         torch.cuda.empty_cache()
         out["extra"] = extra_legs()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_av(args, hp.num_D) if av else cpu_baseline(args)
     if rank == 0:
         emit(out, args)

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -51,12 +52,36 @@ def test_gpus_2_spawns_its_own_ranks_and_exits_cleanly():
     """`python bench.py --gpus 2` with no launcher: bench.py re-runs itself as two ranks under torch.distributed.run; on this
     one-GPU box the ranks share cuda:0 and exchange over gloo (--share-gpu; RCCL refuses two ranks on one device), the bucketed exchange
     of the product step runs, rank 0 prints the one JSON line, and every rank leaves through destroy_process_group (exit status 0)."""
-    out = run_bench("--gpus", "2", "--share-gpu", "--steps", "4", "--warmup", "2", "--batch", "2", "--bins", "128", "--frames", "64",
+    out = run_bench("--full", "--gpus", "2", "--share-gpu", "--steps", "4", "--warmup", "2", "--batch", "2", "--bins", "128", "--frames", "64",
                     "--no-cpu-baseline")
     assert out["n_gpus"] == 2 and out["config"]["parallelism"] == "dp2" and out["config"]["global_batch"] == 4
     assert out["steps"] == 4 and out["warmup"] == 2 and out["scaling"] == "weak" and out["value"] > 0
     assert "comm_ms_exposed" in out["config"] and "ranks_share_devices" in out["config"]
     assert out["roofline"]["family"].endswith(("_f16x2", "_bf16x3", "_f32")) and 0 < out["roofline"]["frac"] < 1
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """a plain run (no --full) times exactly --steps steps and measures nothing else; --dump-outputs writes what the last timed step computed
+    (the generated clips, the six loss scalars, both parameter arenas after the Adam updates), and the same arguments give the same files."""
+    dumps = []
+    for i in range(2):
+        d = str(tmp_path / ("run%d" % i))
+        out = run_bench("--steps", "3", "--warmup", "1", "--batch", "2", "--bins", "128", "--frames", "64", "--dump-outputs", d)
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["n_gpus"] == 1 and out["ms_per_step"] > 0
+        assert abs(out["value"] - 2 * 1e3 / out["ms_per_step"]) < 0.01 * out["value"]
+        for k in ("roofline", "stages", "extra", "cpu_baseline"):
+            assert k not in out, k
+        assert "launch_modes" not in out["config"] and "comm_ms_exposed" not in out["config"]
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64e6
+        dumps.append({f[:-len(".npy")]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    a, b = dumps
+    assert set(a) == {"fake", "losses", "params_G", "params_D"}
+    assert a["fake"].shape == (2, 1, 128, 64) and a["fake"].dtype == np.float32
+    assert a["losses"].shape == (6,) and a["losses"].dtype == np.float64
+    assert a["params_G"].dtype == a["params_D"].dtype == np.float32 and a["params_G"].size > a["params_D"].size > 1000
+    for k in a:
+        assert np.isfinite(a[k]).all() and a[k].shape == b[k].shape, k
+        assert np.allclose(a[k], b[k], rtol=1e-4, atol=1e-6), (k, float(np.abs(a[k] - b[k]).max()))
 
 
 def test_gpus_n_without_devices_or_share_gpu_refuses():
@@ -72,7 +97,7 @@ def test_kernel_families_come_from_the_library():
     kernel instance the step runs, every family priced against the ceiling its suffix names; bench.py holds no dispatch mirror."""
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "viai_conv2d_last_kernel" in src and "mirror of viai_" not in src
-    line, out = run_bench("--steps", "3", "--warmup", "1", detail=True)
+    line, out = run_bench("--full", "--steps", "3", "--warmup", "1", detail=True)
     # the contract line itself: roofline + cpu_baseline of the headline, and a few numbers of each bounded leg
     assert 0 < line["roofline"]["frac"] < 1 and line["roofline"]["bound"] == "mfma" and line["roofline"]["family"] == out["roofline"]["family"]
     assert line["roofline"]["avg_launch_us"] > 0 and line["roofline"]["peak"] > line["roofline"]["achieved"] > 0
@@ -113,7 +138,7 @@ def test_kernel_families_come_from_the_library():
 
 @pytest.mark.parametrize("config", ["av", "av_msd"])
 def test_vision_infused_configs_print_roofline_and_cpu_baseline(config):
-    out = run_bench("--config", config, "--steps", "2", "--warmup", "1", "--batch", "1", "--bins", "256", "--frames", "32")
+    out = run_bench("--full", "--config", config, "--steps", "2", "--warmup", "1", "--batch", "1", "--bins", "256", "--frames", "32")
     assert out["config"]["workload"].startswith("configs[%d]" % (2 if config == "av" else 3))
     rf = out["roofline"]
     assert rf["bound"] == "mfma" and 0 < rf["frac"] < 1 and rf["family"] in rf["frac_by_kernel"]
@@ -122,7 +147,7 @@ def test_vision_infused_configs_print_roofline_and_cpu_baseline(config):
 
 
 def test_wavenet_config_prints_the_synthesis_line():
-    out = run_bench("--config", "wavenet", "--steps", "192", "--warmup", "64")
+    out = run_bench("--full", "--config", "wavenet", "--steps", "192", "--warmup", "64")
     assert out["unit"] == "samples/s" and out["steps"] == 192 and out["value"] > 1000
     rf = out["roofline"]
     assert rf["bound"] == "hbm" and rf["unit"] == "GB/s" and 0 < rf["frac"] < 1 and 90e6 < rf["algorithmic_bytes_per_step"] < 110e6

@@ -1,7 +1,7 @@
 # round-6 evidence run: bench line (the driver's command line), kernel stats + queue report of the three-stream step, single-stream timeline, counters of the step and of the
 # dominant kernel's layer, the other configs' kernel stats, the WaveNet pipeline's counters and stage stamps.   bash tools/r06_final.sh <tag>
 tag=$1; o=gpurun_out/r06_$tag; mkdir -p $o
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $o/bench.log 2> $o/bench.err; tail -1 $o/bench.log > $o/bench_line.json; cp gpurun_out/bench_detail_audio.json $o/bench_detail.json
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --detail $o/bench_detail.json > $o/bench.log 2> $o/bench.err; tail -1 $o/bench.log > $o/bench_line.json
 tools/step_profile.sh $o r06_$tag > $o/step_profile.log 2>&1
 tools/pmc_step.sh $o/pmc_step.json > $o/pmc_step.log 2>&1
 tools/pmc_layer.sh $o/pmc_dconv3.json --shape 16 64 32 256 512 --bn --p16 > /dev/null 2>&1
