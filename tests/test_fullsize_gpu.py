@@ -1,8 +1,11 @@
-"""Full-size checks (BASELINE.json configs[1]: batch 16, 256 x 256 mel): the kernels the benchmark times, at the shapes it times.
+"""Full-size checks (BASELINE.json configs[1]: batch 16, 256 x 256 mel): kernel instances at the shapes the benchmark times.
 
 The layers of the benchmark size select other kernel instances than the cfg 0 / cfg 1 shapes (128 x 256 wide halo tile, patch-staged
 stride-2 forward / data gradient, register-filter halo kernel, split-K, row-run streaming kernels, all-taps weight gradient ...).
-They are pinned three ways:
+The tests here feed fp32 tensors, so every forward and data gradient below runs on the register-staged (fp32-input) kernels; in the step
+most layers take their input pre-split (P16) from the BatchNorm before them and run on the loader / consumer kernels instead.  Those
+launches, as the step makes them, are replayed against fp64 by tests/test_step_launches_gpu.py, which also checks that every layer
+shape listed here still occurs in the step.  The fp32-input kernels are pinned here three ways:
 
 * VALUES, layer by layer: forward, data gradient and weight gradient of every distinct layer shape of the cfg-2 step against
   torch.nn.functional on the CPU in fp64 (the reference's own ops: Discriminator_Networks.py:37-50, New_Inpainting_Networks.py:70-89,
@@ -41,9 +44,12 @@ FULL_LAYERS = [
     ("G.conv6_2 32->1 @256x256 (row-run streaming)", 16, 256, 256, 32, 1, (3, 3), (1, 1), (1, 1), True),
     ("D.conv1 1->64 1x4 s(1,2) (Cin = 1 streaming)", 16, 256, 256, 1, 64, (1, 4), (1, 2), (0, 1), False),
 ]
+# kernel classes kept at full size whose shape the current step does not launch (at 64 x 128 the step runs the virtual concat
+# cat(64, 64) -> 32): tests/test_step_launches_gpu.py fails if one of them comes back, or another layer listed here goes
+NOT_IN_STEP = ("G 64->64 @64x128 (streamed-filter halo)", "E deep 512->512 @8x8 (split-K)")
 
-# the remaining layer shapes of the cfg-2 step (SURVEY.md section 8a per-layer table), so that EVERY conv launch the benchmark
-# times has a value test at its own shape; (.., C2) = channels of the virtually concatenated second source
+# the remaining layer shapes of the cfg-2 step (SURVEY.md section 8a per-layer table), each with a value test of the fp32-input kernels at its
+# own shape; (.., C2) = channels of the virtually concatenated second source
 MORE_LAYERS = [
     ("E.conv1 1->32 s2 @256x256 (Cin = 1 streaming)", 16, 256, 256, 1, 32, (3, 3), (2, 2), (1, 1), False, 0),
     ("E.conv2 32->64 s(2,1) @128x128", 16, 128, 128, 32, 64, (3, 3), (2, 1), (1, 1), False, 0),

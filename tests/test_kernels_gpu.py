@@ -313,9 +313,16 @@ def test_conv_bn_act_train_matches_torch_cpu(act, shape):
     assert int(bng.num_batches_tracked) == 1
 
 
+# (N, H, W, Cout, kernel, stride, padding[, P16 output]); the last four are the benchmark's layers as the step runs them: E.conv1 at 16 x 256 x 256
+# and D.conv1 at the three scales of the 3-scale D, z written pre-split (tests/test_step_launches_gpu.py maps the step's launches here)
+CIN1_GEOMS = [(3, 80, 96, 32, (3, 3), (2, 2), (1, 1)), (2, 64, 72, 64, (1, 4), (1, 2), (0, 1)), (5, 33, 37, 32, (3, 3), (2, 2), (1, 1)),
+              (2, 32, 128, 64, (1, 4), (1, 2), (0, 1)), (2, 64, 64, 32, (3, 3), (2, 2), (1, 1)),
+              (16, 256, 256, 32, (3, 3), (2, 2), (1, 1), True), (16, 256, 256, 64, (1, 4), (1, 2), (0, 1), True),
+              (16, 128, 128, 64, (1, 4), (1, 2), (0, 1), True), (16, 64, 64, 64, (1, 4), (1, 2), (0, 1), True)]
+
+
 @pytest.mark.parametrize("need_dx", [False, "fused", "apply"])
-@pytest.mark.parametrize("geom", [(3, 80, 96, 32, (3, 3), (2, 2), (1, 1)), (2, 64, 72, 64, (1, 4), (1, 2), (0, 1)), (5, 33, 37, 32, (3, 3), (2, 2), (1, 1)),
-                                  (2, 32, 128, 64, (1, 4), (1, 2), (0, 1)), (2, 64, 64, 32, (3, 3), (2, 2), (1, 1))])
+@pytest.mark.parametrize("geom", CIN1_GEOMS)
 def test_cin1_conv_bn_layer_without_the_stored_preactivation(geom, need_dx, monkeypatch):
     """E.conv1 / D.conv1 (Inpainting_Networks.py:55,71; Discriminator_Networks.py:17-19): Cin = 1 conv -> BatchNorm2d(train) ->
     LeakyReLU on the fused path (viai_conv2d_cin1_bn_*: the conv output is never stored, forward and backward recompute it from x;
@@ -325,10 +332,12 @@ def test_cin1_conv_bn_layer_without_the_stored_preactivation(geom, need_dx, monk
     geometries take the input-pixel-mapped kernel, slower than "apply" and opt-in).  Forward, dw, dgamma, dbeta,
     dx and the running statistics against fp64 within 5x of torch-CPU-fp32's own rounding error; the third geometry has a ragged last
     statistics block (pixels not a multiple of 256); the last two have blocks of whole output rows, i.e. the kernels that stage the
-    block's input rows in LDS (the benchmark shapes take that path)."""
+    block's input rows in LDS (the benchmark shapes take that path).  The benchmark geometries write z pre-split, as the step does
+    (viai_conv2d_cin1_bn_fwd_p16): the decoded z is compared."""
     from viai_amd import ops, _lib
     monkeypatch.setenv("VIAI_CIN1_BN_DGRAD", "0" if need_dx == "apply" else "1")
-    N, H, W, Co, k, s_, p_ = geom
+    N, H, W, Co, k, s_, p_ = geom[:7]
+    out_p16 = len(geom) > 7 and geom[7]
     x = O.cf_uniform("c1.x", (N, 1, H, W), 0, 1)
     w = O.cf_std("c1.w", (Co, 1) + k, 0.3)
     g = O.cf_uniform("c1.g", (Co,), 0.8, 1.2)
@@ -345,10 +354,18 @@ def test_cin1_conv_bn_layer_without_the_stored_preactivation(geom, need_dx, monk
     xg = nhwc(x).requires_grad_(bool(need_dx))
     wg = w.cuda().requires_grad_(True)
     d = ops.conv_desc(N, H, W, 1, 0, Co, k[0], k[1], s_[0], s_[1], p_[0], p_[1], 0, 1, 1, -1, -1)
-    assert _lib.load().viai_conv2d_cin1_bn_ok(d["ref"]) == 1
-    zg = ops.conv_bn_act(xg, wg, None, bn, kernel=k, stride=s_, padding=p_, act=ops.ACT_LRELU)
+    lib = _lib.load()
+    assert lib.viai_conv2d_cin1_bn_ok(d["ref"]) == 1
+    calls = []
+    orig = lib.viai_conv2d_cin1_bn_fwd_p16
+    lib.viai_conv2d_cin1_bn_fwd_p16 = lambda *a: (calls.append(1), orig(*a))[1]
+    try:
+        zg = ops.conv_bn_act(xg, wg, None, bn, kernel=k, stride=s_, padding=p_, act=ops.ACT_LRELU, out_p16=out_p16)
+    finally:
+        lib.viai_conv2d_cin1_bn_fwd_p16 = orig
+    assert len(calls) == (1 if out_p16 and ops.P16 else 0) and ops.is_p16(zg) == bool(calls)
     zg.backward(nhwc(gy))
-    hip = (nchw(zg), nchw(xg.grad) if need_dx else None, wg.grad, bn.weight.grad, bn.bias.grad)
+    hip = (nchw(ops.p16_decode(zg)), nchw(xg.grad) if need_dx else None, wg.grad, bn.weight.grad, bn.bias.grad)
     for nm, h, c32, t in zip(("z", "dx", "dw", "dgamma", "dbeta"), hip, cpu32, truth):
         if h is not None:
             assert relerr(h, t) < 5 * relerr(c32, t) + 1e-6, (nm, relerr(h, t), relerr(c32, t))
@@ -727,7 +744,15 @@ def test_f16x2_range_guard_counts_saturating_operands():
         ops.range_report()
 
 
-@pytest.mark.parametrize("case", ["G.conv6", "D.conv3-4", "D.eval", "wide-frozen"])
+# (N, Cin, C of the middle tensor, H, W); "... full" / "... msd<i>": the pairs networks.py builds in the benchmark's steps -- G.conv6 at
+# 16 x 256 x 256 and D.conv3-4 at 16 x 64 x 32 and at scale 1 of the 3-scale D (scale 2 runs the two layers) (tests/test_step_launches_gpu.py maps the step's launches here)
+PAIR_CASES = {"G.conv6": (2, 32, 32, 32, 64), "D.conv3-4": (2, 64, 512, 16, 32), "D.eval": (2, 32, 64, 8, 16), "wide-frozen": (3, 128, 256, 8, 48),
+              "G.conv6 full": (16, 32, 32, 256, 256), "D.conv3-4 full": (16, 256, 512, 64, 32), "D.conv3-4 msd1": (16, 256, 512, 32, 16)}
+
+PAIR_BWD = {"G.conv6 full": "viai_pair_cout1_bn_bwd_p16", "D.conv3-4 full": "viai_pair_cout1_bn_bwd_p16", "D.conv3-4 msd1": "viai_pair_cout1_bn_bwd_p16"}
+
+
+@pytest.mark.parametrize("case", list(PAIR_CASES))
 def test_fused_bn_cout1_pair_matches_the_two_layers(case):
     """(conv + BatchNorm + act) -> (3 x 3 conv to ONE channel) as one op (ops.conv_bn_act_cout1: the tensor between the layers and the
     second layer's data gradient are never stored; csrc/conv_direct.hip viai_pair_cout1_*) against the same two layers run one after the
@@ -735,9 +760,8 @@ def test_fused_bn_cout1_pair_matches_the_two_layers(case):
     New_Inpainting_Networks.py:85-88), D.conv3 + BN + LeakyReLU -> conv4 + Sigmoid (512 channels; Discriminator_Networks.py:44-49),
     eval-mode BatchNorm, and a frozen pair (data gradient only: the G step's pass through D)."""
     from viai_amd import networks as N_, ops
-    tr = case == "G.conv6"
-    N, Ci, Cm, H, W = {"G.conv6": (2, 32, 32, 32, 64), "D.conv3-4": (2, 64, 512, 16, 32), "D.eval": (2, 32, 64, 8, 16),
-                       "wide-frozen": (3, 128, 256, 8, 48)}[case]
+    tr = case.startswith("G.conv6")
+    N, Ci, Cm, H, W = PAIR_CASES[case]
     act = ops.ACT_RELU if tr else ops.ACT_LRELU
     mk = (lambda ci, co: torch.nn.ConvTranspose2d(ci, co, 3, 1, 1, bias=True)) if tr else (lambda ci, co: torch.nn.Conv2d(ci, co, 3, 1, 1, bias=False))
     conv1, conv2, bn = mk(Ci, Cm).cuda(), mk(Cm, 1).cuda(), torch.nn.BatchNorm2d(Cm).cuda()
@@ -773,13 +797,17 @@ def test_fused_bn_cout1_pair_matches_the_two_layers(case):
         return out
     calls = []
     lib = ops._lib.load()
-    orig = lib.viai_pair_cout1_bn_bwd
+    names = ("viai_pair_cout1_bn_bwd", "viai_pair_cout1_bn_bwd_p16")
+    origs = {n: getattr(lib, n) for n in names}
     try:
-        lib.viai_pair_cout1_bn_bwd = lambda *a: (calls.append(1), orig(*a))[1]
+        for n in names:
+            setattr(lib, n, (lambda n_, f_: lambda *a: (calls.append(n_), f_(*a))[1])(n, origs[n]))
         fused = run(True)
     finally:
-        lib.viai_pair_cout1_bn_bwd = orig
-    assert calls == [1]                                   # the pair kernels really ran
+        for n in names:
+            setattr(lib, n, origs[n])
+    # the pair kernels really ran; at the benchmark's sizes the front layer's dy is written pre-split, as in the step
+    assert calls == [PAIR_BWD.get(case, "viai_pair_cout1_bn_bwd")], calls
     plain = run(False)
     assert len(fused) == len(plain)
     for i, (a, b) in enumerate(zip(fused, plain)):
