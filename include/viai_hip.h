@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VIAI_ABI_VERSION 17
+#define VIAI_ABI_VERSION 18
 
 enum { VIAI_ACT_NONE = 0, VIAI_ACT_RELU = 1, VIAI_ACT_LRELU = 2, VIAI_ACT_SIGMOID = 3 };
 
@@ -131,6 +131,16 @@ int viai_conv2d_wgrad_f16(const viai_conv2d* c, const float* x, const float* x2,
  * ceiling of that arithmetic.  buf receives the NUL-terminated name (truncated to cap); returns the launch count, 0 if none.
  * (measurement aid: no reference counterpart)                                                                             */
 int viai_conv2d_last_kernel(char* buf, int cap);
+/* (ABI 18) The same answer without a launch (host code only): the family name viai_conv2d_last_kernel would report after the launch of
+ * this layer in direction `pass` (0 forward, 1 data gradient, 2 weight gradient) with operands of `form`, written to family
+ * (NUL-terminated, truncated to cap); returns the number of conv-kernel launches, 0 with an empty name if the entry point would
+ * refuse the call.  (Cin = 1 / Cout = 1 layers answer 1 x "direct" like the tag: the streaming kernels check strides and channel
+ * counts of their own at the launch, after the tag is set.)  form: VIAI_FORM_F32 (viai_conv2d_fwd / _dgrad / _wgrad), VIAI_FORM_AMAX (the _amax / _f16 entry points),
+ * VIAI_FORM_P16 (the _p16 entry points); for the weight gradient's P16 form add its flags: VIAI_FORM_P16 | (flags << 2).       */
+#define VIAI_FORM_F32 0
+#define VIAI_FORM_AMAX 1
+#define VIAI_FORM_P16 2
+int viai_conv2d_route(const viai_conv2d* c, int pass, int form, char* family, int cap);
 
 /* generic weight repack used by the two pack entry points (exposed for tests):
  * wp[no][t][ki] = w[no*s_no + ki*s_ki + t]                                       */
@@ -142,7 +152,9 @@ int viai_pack_weight(const float* w, float* wp, int n_out, int k_in, int taps,
  * (Inpainting_Networks.py:72-76, New_Inpainting_Networks.py:33-36,72-75,86,
  *  Discriminator_Networks.py:39-46).                                            */
 /* merge block partials -> mean / invstd / (scale, shift); update running stats
- * (momentum, unbiased variance) and num_batches_tracked (int64, may be NULL).    */
+ * (momentum, unbiased variance) and num_batches_tracked (int64, may be NULL).
+ * Not for the partials of a viai_conv2d_fwd_p16 launch on a layer that reports VIAI_P16_OK_FWD_LIN: those are laid out for
+ * viai_bn_finalize_lin below.                                                    */
 int viai_bn_finalize(const float* stat_part, int nblk, int rows_per_blk, long M, int C,
                      const float* gamma, const float* beta, float* running_mean, float* running_var,
                      int64_t* num_batches_tracked, float momentum, float eps,
@@ -540,7 +552,9 @@ int viai_bn_join_bwd_p16(const float* dz, const float* dz2, const float* zj, flo
                          long M, int C, int training, float* amax, void* stream);
 /* x (fp32) = the values a P16 tensor holds, (lead + rem) / S(*amax) */
 int viai_p16_decode(const float* p16, float* x, long M, int C, const float* amax, void* stream);
-/* viai_conv2d_fwd_amax / viai_conv2d_dgrad_f16 with the gathered tensor pre-split (one source; scale from *x_amax / *dy_amax) */
+/* viai_conv2d_fwd_amax / viai_conv2d_dgrad_f16 with the gathered tensor pre-split (one source; scale from *x_amax / *dy_amax).
+ * On a layer that reports VIAI_P16_OK_FWD_LIN the forward writes stat_part in the linear-tile layout: finalize it with
+ * viai_bn_finalize_lin, never with viai_bn_finalize / _tiles (fp32-form launches of the same layer keep viai_conv2d_stat_geom's layout). */
 int viai_conv2d_fwd_p16(const viai_conv2d* c, const float* x, const float* wp_fwd, const float* bias, float* y, float* stat_part,
                         int act, const float* x_amax, void* stream);
 int viai_conv2d_dgrad_f16_p16(const viai_conv2d* c, const float* dy, const float* wp, float* dx, float* dx2,

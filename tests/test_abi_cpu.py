@@ -72,6 +72,17 @@ def test_invalid_descriptors_are_rejected(lib):
     assert lib.viai_conv2d_stat_geom(C.byref(bad), C.byref(nblk), C.byref(rows)) != 0
     assert lib.viai_conv2d_wgrad_ws_bytes(C.byref(bad)) == 0
     assert lib.viai_conv2d_fwd(C.byref(bad), 0, 0, 0, 0, 0, 0, 0, 0) != 0
+    # Cin = 1 outside the streaming kernels' 32 / 64 / 128 output channels (its weight gradient once divided by zero): refused in every
+    # direction and by every query alike
+    bad = Conv2dDesc(1, 256, 256, 1, 0, 1, 3, 3, 1, 1, 1, 1, 0, 0, 0, -1, -1)
+    fam = C.create_string_buffer(64)
+    assert lib.viai_conv2d_stat_geom(C.byref(bad), C.byref(nblk), C.byref(rows)) != 0
+    assert lib.viai_conv2d_wgrad_ws_bytes(C.byref(bad)) == 0
+    assert lib.viai_conv2d_fwd(C.byref(bad), 0, 0, 0, 0, 0, 0, 0, 0) != 0
+    assert lib.viai_conv2d_dgrad(C.byref(bad), 0, 0, 0, 0, 0) != 0
+    assert lib.viai_conv2d_wgrad(C.byref(bad), 0, 0, 0, 0, 0, 0, 0, 0) != 0
+    for p in (0, 1, 2):
+        assert lib.viai_conv2d_route(C.byref(bad), p, 0, fam, 64) == 0 and fam.value == b""
 
 
 def test_module_shells_have_the_reference_state_dict():

@@ -129,13 +129,13 @@ def run_census(model, steps=1):
             d = getattr(args[0], "_obj", None) if args else None
             if not isinstance(d, _lib.Conv2dDesc):
                 return r
-            lib.viai_conv2d_last_kernel(buf, 64)
+            nl = lib.viai_conv2d_last_kernel(buf, 64)
             fam = buf.value.decode()
             rest = args[1:]
             opts = tuple(sorted((k, int(rest[i] or 0) if k in VALUE_ROLES else bool(rest[i])) for k, i in roles.items()))
             key = (name, _desc_tuple(d), fam, opts)
             if key not in seen:
-                seen[key] = {"entry": name, "desc": list(key[1]), "family": fam, "opts": dict(opts), "count": 0}
+                seen[key] = {"entry": name, "desc": list(key[1]), "family": fam, "launches": nl, "opts": dict(opts), "count": 0}
             seen[key]["count"] += 1
             return r
         return spy
@@ -480,6 +480,24 @@ def _replayable(rec):
     return rec["entry"] in ROLES
 
 
+# (pass, form) of viai_conv2d_route for the launch entry points (include/viai_hip.h: VIAI_FORM_*)
+ROUTE_OF = {"viai_conv2d_fwd": (0, 0), "viai_conv2d_fwd_amax": (0, 1), "viai_conv2d_fwd_p16": (0, 2),
+            "viai_conv2d_dgrad": (1, 0), "viai_conv2d_dgrad_f16": (1, 1), "viai_conv2d_dgrad_f16_p16": (1, 2),
+            "viai_conv2d_wgrad": (2, 0), "viai_conv2d_wgrad_f16": (2, 1), "viai_conv2d_wgrad_f16_p16": (2, 2)}
+
+
+def _route(lib, rec):
+    """(family, launches) viai_conv2d_route predicts for a census record"""
+    from viai_amd._lib import Conv2dDesc
+    p, f = ROUTE_OF[rec["entry"]]
+    if rec["entry"] == "viai_conv2d_wgrad_f16_p16":
+        f = (f | (rec["opts"]["flags"] << 2)) if rec["opts"]["flags"] else 1          # (no flags: the plain f16x2 form)
+    buf = C.create_string_buffer(64)
+    d = Conv2dDesc(*rec["desc"])
+    n = lib.viai_conv2d_route(C.byref(d), p, f, buf, 64)
+    return buf.value.decode(), n
+
+
 def replay_all(records, label, out=print):
     """replay every record, collecting (row, failure or None); one table printed"""
     gen = torch.Generator(device="cuda").manual_seed(20261016)
@@ -546,6 +564,13 @@ def test_census_is_complete(census):
     assert c["cfg1"] and c["cfg3"]
     assert any(r["entry"] == "viai_conv2d_fwd_p16" for r in c["cfg1"])
     assert any(r["entry"] == "viai_conv2d_fwd_p16" for r in c["cfg3"])
+    from viai_amd import _lib
+    lib = _lib.load()
+    routed = [r for r in allrec if r["entry"] in ROUTE_OF]
+    assert routed
+    off = ["%s %s: launched %s x%d, route %s x%d" % ((r["entry"], _Geom(tuple(r["desc"])).short(), r["family"], r["launches"]) + _route(lib, r))
+           for r in routed if _route(lib, r) != (r["family"], r["launches"])]
+    assert not off, "viai_conv2d_route disagrees with the launch:\n  " + "\n  ".join(off)
     shapes = {(r["desc"][0], r["desc"][1], r["desc"][2], r["desc"][3] + r["desc"][4], r["desc"][5], (r["desc"][6], r["desc"][7]),
                (r["desc"][8], r["desc"][9]), (r["desc"][10], r["desc"][11]), bool(r["desc"][12])) for r in c["cfg1"]}
     fs = _load_test_module("test_fullsize_gpu")

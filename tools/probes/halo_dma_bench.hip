@@ -33,11 +33,11 @@ int main(int argc, char** argv) {
     viai_dma_prof_buf = dprof;
 #endif
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    for (int i = 0; i < 3; ++i) if (int e = viai_conv_halo_c32_dma_launch(a, -1, -1, slots, 0)) { printf("launch error %d\n", e); return 1; }
+    for (int i = 0; i < 3; ++i) if (int e = viai_conv_halo_c32_dma_launch(a, 0)) { printf("launch error %d\n", e); return 1; }
     hipDeviceSynchronize();
     std::vector<float> ts;
     for (int i = 0; i < iters; ++i) {
-        hipEventRecord(e0, 0); viai_conv_halo_c32_dma_launch(a, -1, -1, slots, 0); hipEventRecord(e1, 0); hipEventSynchronize(e1);
+        hipEventRecord(e0, 0); viai_conv_halo_c32_dma_launch(a, 0); hipEventRecord(e1, 0); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1); ts.push_back(ms * 1e3f);
     }
     std::sort(ts.begin(), ts.end());

@@ -22,7 +22,7 @@ class ViaiLibraryError(RuntimeError):
 
 # ABI version THIS file's SIGNATURES / struct mirrors were written against: bumped together with them.  load() compares it with the
 # library, and with the committed header where that is present (a source checkout), so a stale _lib.py cannot call a rebuilt .so.
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 def _header_abi_version():
@@ -89,6 +89,7 @@ SIGNATURES = {
     "viai_conv2d_wgrad_ws_bytes": (C.c_size_t, [_CP]),
     "viai_conv2d_wgrad": (_I, [_CP, _P, _P, _P, _P, _P, _P, _I, _P]),
     "viai_conv2d_last_kernel": (_I, [C.c_char_p, _I]),
+    "viai_conv2d_route": (_I, [_CP, _I, _I, C.c_char_p, _I]),
     "viai_step_scalars": (_I, [_P, _P, _P, _P, _P, _F, _F, _P, _P]),
     "viai_pack_weight": (_I, [_P, _P, _I, _I, _I, _L, _L, _P]),
     "viai_bn_finalize": (_I, [_P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P]),

@@ -33,8 +33,14 @@ static inline int kind_of(const viai_conv2d* c) {
     return K_IGEMM;
 }
 
+// the Cin = 1 streaming kernels exist for these windows and channel counts only (conv_direct.hip)
+static inline bool cin1_ok(const viai_conv2d* c) {
+    const bool win = (c->kh == 3 && c->kw == 3) || (c->kh == 1 && (c->kw == 1 || c->kw == 3 || c->kw == 4 || c->kw == 6));
+    return win && (c->Cout == 32 || c->Cout == 64 || c->Cout == 128);
+}
 static inline bool valid(const viai_conv2d* c) {
     if (!c || c->N <= 0 || c->IH <= 0 || c->IW <= 0 || c->C1 <= 0 || c->C2 < 0 || c->Cout <= 0) return false;
+    if (cin_of(c) == 1 && !cin1_ok(c)) return false;
     const bool runk = (cin_of(c) > 1 && cin_of(c) <= 4 && c->Cout > 1);     // row-run kind: taps are kernel rows
     if (c->kh <= 0 || c->kw <= 0) return false;
     if (runk ? (c->kh > VIAI_MAX_TAPS || c->kw > 8) : (c->kh * c->kw > VIAI_MAX_TAPS)) return false;
@@ -54,129 +60,11 @@ static bool bf3_enabled() {
     if (v < 0) { const char* e = getenv("VIAI_MATH"); v = (e && (!strcmp(e, "fp32") || !strcmp(e, "f32"))) ? 0 : 1; }
     return v == 1;
 }
-static bool use_bf3_shape(long M, int n_out, int k_in) {
-    (void)M; (void)n_out;
-    return bf3_enabled() && (k_in % 16) == 0;
-}
-// GEMM rows that decide the bf16x3 weight layout (pack and launch must agree; dgrad uses its largest parity class)
-static long bf3_rows_fwd(const viai_conv2d* c) { int oh, ow; viai_conv2d_out_hw(c, &oh, &ow); return (long)c->N * oh * ow; }
-static long bf3_rows_dgrad(const viai_conv2d* c) { return (long)c->N * ((c->IH + c->sh - 1) / c->sh) * ((c->IW + c->sw - 1) / c->sw); }
-
-static bool use_bf3_fwd(const viai_conv2d* c);
-static bool use_bf3_dgrad(const viai_conv2d* c);
-static bool s2_dgrad(const viai_conv2d* c);
-static bool f16x2_enabled();
-static bool frag_dgrad(const viai_conv2d* c);
-// LDS-resident-tile kernel (conv_halo_bf3.hip) for the small-channel stride-1 layers
-static bool halo_fwd(const viai_conv2d* c) {
-    if (!use_bf3_fwd(c)) return false;
-    ConvGeom g{}; viai_geom_fwd(c, &g);
-    return viai_conv_halo_ok(g, c->C1, c->C2, c->Cout);
-}
-static bool halo_dgrad(const viai_conv2d* c) {
-    if (!use_bf3_dgrad(c) || c->sw != 1 || (c->sh != 1 && c->sh != 2)) return false;
-    if (c->sh == 2) {                                      // round 6: the stride-(2, 1) layer (MelEncoder.conv2): both row-parity classes on the halo kernel
-        if (!f16x2_enabled() || c->transposed) return false;
-        for (int a_ = 0; a_ < 2; ++a_) {
-            ConvGeom g{}; if (viai_geom_dgrad_class(c, a_, 0, &g) == 0) return false;
-            if (!viai_conv_halo_ok(g, c->Cout, 0, cin_of(c))) return false;
-        }
-        return true;
-    }
-    ConvGeom g{}; if (viai_geom_dgrad_class(c, 0, 0, &g) == 0) return false;
-    return viai_conv_halo_ok(g, c->Cout, 0, cin_of(c));
-}
-// f16x2 halo kernel with the filter in registers (32 -> <= 32 channels, full 3 x 3 window)
-static bool halo16_fwd(const viai_conv2d* c) {
-    if (!f16x2_enabled() || !halo_fwd(c)) return false;
-    ConvGeom g{}; viai_geom_fwd(c, &g);
-    return viai_conv_halo16_ok(g, c->C1, c->C2, c->Cout);
-}
-static bool halo16_dgrad(const viai_conv2d* c) {
-    if (!f16x2_enabled() || !halo_dgrad(c)) return false;
-    ConvGeom g{}; viai_geom_dgrad_class(c, 0, 0, &g);
-    return viai_conv_halo16_ok(g, c->Cout, 0, cin_of(c));
-}
-// weight layout of the bf16x3 kernels: fragment-major for the wide-tile and halo kernels, planar otherwise
+// f16x2 (two fp16 terms per operand) for every split-precision kernel that has the form; VIAI_F16X2=0 keeps them on bf16x3
 static bool f16x2_enabled() {
     static int on = -1;
     if (on < 0) { const char* e = getenv("VIAI_F16X2"); on = e ? atoi(e) : 1; }
     return on != 0;
-}
-// wide halo kernel (conv_halo_bf3.hip, f16x2 fragment-major weights): stride-1 3 x 3 layers with Cin >= 32 and 32 / 64 / 128k outputs
-static bool halo_wide_fwd(const viai_conv2d* c) {
-    if (!f16x2_enabled() || !use_bf3_fwd(c)) return false;
-    ConvArgs a{};
-    viai_geom_fwd(c, &a.g);
-    a.C1 = c->C1; a.C2 = c->C2; a.Cout = c->Cout; a.OC1 = c->Cout; a.M = a.g.N * a.g.OH * a.g.OW;
-    return viai_conv_halo_wide_ok(a);
-}
-static bool halo_wide_dgrad(const viai_conv2d* c) {
-    if (!f16x2_enabled() || !use_bf3_dgrad(c) || c->sh != 1 || c->sw != 1) return false;
-    ConvArgs a{};
-    if (viai_geom_dgrad_class(c, 0, 0, &a.g) == 0) return false;
-    a.C1 = c->Cout; a.C2 = 0; a.Cout = cin_of(c); a.OC1 = c->C1; a.M = a.g.N * a.g.SH * a.g.SW;
-    return viai_conv_halo_wide_ok(a);
-}
-// loader / consumer kernel over linear pixel tiles (conv_halo_dma.hip, round 5): stride-1 3 x 3 layers on maps that are not whole 8 x 16 tiles, when
-// the operand arrives pre-split (geometry only here: the launch decides by a.in_p16)
-static bool lin_fwd(const viai_conv2d* c) {
-    if (!f16x2_enabled() || !use_bf3_fwd(c)) return false;
-    ConvArgs a{};
-    viai_geom_fwd(c, &a.g);
-    a.C1 = c->C1; a.C2 = c->C2; a.Cout = c->Cout; a.OC1 = c->Cout; a.M = a.g.N * a.g.OH * a.g.OW;
-    return viai_conv_lin_dma_geom_ok(a);
-}
-static bool lin_dgrad(const viai_conv2d* c) {
-    if (!f16x2_enabled() || !use_bf3_dgrad(c) || c->sh != 1 || c->sw != 1) return false;
-    ConvArgs a{};
-    if (viai_geom_dgrad_class(c, 0, 0, &a.g) == 0) return false;
-    a.C1 = c->Cout; a.C2 = 0; a.Cout = cin_of(c); a.OC1 = c->C1; a.M = a.g.N * a.g.SH * a.g.SW;
-    return viai_conv_lin_dma_geom_ok(a);
-}
-// f16x2 for the LDS-weight / split-K kernels too (planar fp16 planes); VIAI_F16_PLANAR=0 keeps them on bf16x3
-static bool planar16_enabled() {
-    constexpr int on = 1;
-    return on != 0 && f16x2_enabled();
-}
-// forward weight layout: 0 planar bf16x3, 1 fragment-major bf16x3, 3 fragment-major f16x2 (wide-tile / halo kernels), 4 planar f16x2
-static int frag_fwd(const viai_conv2d* c) {
-    if (halo_fwd(c)) return f16x2_enabled() ? 3 : 1;            // f16x2: filter in registers (32 -> <= 32 channels) or streamed
-    if (viai_bf3_frag_layout(bf3_rows_fwd(c), c->Cout)) return f16x2_enabled() ? 3 : 1;
-    if (halo_wide_fwd(c) || lin_fwd(c)) return 3;
-    return planar16_enabled() ? 4 : 0;
-}
-// data gradient on the f16x2 wide-tile kernel (needs the abs-max of dy): the layers whose classes run on the fragment-major kernel
-static bool dgrad_f16(const viai_conv2d* c) {
-    if (!f16x2_enabled() || !use_bf3_dgrad(c)) return false;
-    if (halo_dgrad(c)) return true;
-    if (halo_wide_dgrad(c) || lin_dgrad(c)) return true;
-    if (!frag_dgrad(c)) return planar16_enabled();              // LDS-weight / split-K kernels: planar fp16 planes
-    return s2_dgrad(c) || viai_bf3_frag_layout(bf3_rows_dgrad(c), cin_of(c));
-}
-static bool sk_fwd(const viai_conv2d* c) {
-    const int lay = frag_fwd(c);                            // planar layouts only (bf16x3 or f16x2)
-    return use_bf3_fwd(c) && (lay == 0 || lay == 4) && viai_bf3_sk_ok(bf3_rows_fwd(c), c->Cout, c->C1, c->C2);
-}
-static bool s2_dgrad(const viai_conv2d* c) { return use_bf3_dgrad(c) && viai_dgrad_s2_ok(c); }     // fused parity classes (conv_dgrad_s2_bf3.hip)
-static bool frag_dgrad(const viai_conv2d* c) { return halo_dgrad(c) || s2_dgrad(c) || viai_bf3_frag_layout(bf3_rows_dgrad(c), cin_of(c)); }
-// layout of the f16x2 data-gradient image: fragment-major also for the wide halo kernel's layers
-static bool frag_dgrad16(const viai_conv2d* c) { return frag_dgrad(c) || halo_wide_dgrad(c) || lin_dgrad(c); }
-
-static bool use_bf3_fwd(const viai_conv2d* c) {
-    if (kind_of(c) != K_IGEMM) return false;
-    int oh, ow; viai_conv2d_out_hw(c, &oh, &ow);
-    return use_bf3_shape((long)c->N * oh * ow, c->Cout, cin_of(c));
-}
-static bool use_bf3_dgrad(const viai_conv2d* c) {
-    if (kind_of(c) != K_IGEMM) return false;
-    for (int a_ = 0; a_ < c->sh; ++a_)
-        for (int b_ = 0; b_ < c->sw; ++b_) {
-            ConvGeom g; int nt = viai_geom_dgrad_class(c, a_, b_, &g);
-            if (g.SH <= 0 || g.SW <= 0 || nt == 0) continue;
-            if (!use_bf3_shape((long)g.N * g.SH * g.SW, cin_of(c), c->Cout)) return false;
-        }
-    return true;
 }
 
 extern "C" int viai_abi_version(void) { return VIAI_ABI_VERSION; }
@@ -185,13 +73,11 @@ thread_local ViaiKernelTag viai_kernel_tag = {nullptr, 0};
 // name of the kernel family the LAST convolution entry point of this thread (viai_conv2d_fwd / _dgrad[_f16] / _wgrad[_f16] /
 // viai_conv2d_cin1_bn_*) launched, copied into buf (NUL-terminated, truncated to cap); returns the number of conv-kernel launches of
 // that call (a strided data gradient on the gather kernel is one launch per parity class), 0 if none.
+static void copy_name(char* buf, int cap, const char* s) {
+    if (buf != nullptr && cap > 0) { strncpy(buf, s ? s : "", cap - 1); buf[cap - 1] = 0; }
+}
 extern "C" int viai_conv2d_last_kernel(char* buf, int cap) {
-    if (buf != nullptr && cap > 0) {
-        const char* s = viai_kernel_tag.family ? viai_kernel_tag.family : "";
-        int i = 0;
-        for (; i < cap - 1 && s[i]; ++i) buf[i] = s[i];
-        buf[i] = 0;
-    }
+    copy_name(buf, cap, viai_kernel_tag.family);
     return viai_kernel_tag.launches;
 }
 
@@ -244,12 +130,6 @@ static void geom_run(const viai_conv2d* c, ConvGeom* g) {
     g->run = 1;
     g->ntaps = g->wtaps = c->kh;
     for (int r = 0; r < c->kh; ++r) { g->dy[r] = r - c->ph; g->dx[r] = -c->pw; g->ws[r] = r; }
-}
-// the ResNet stem (7 x 7, stride 2, 64 channels) on the f16x2 kernels of conv_stem.hip
-static bool stem_f16(const viai_conv2d* c) {
-    if (kind_of(c) != K_RUN || !f16x2_enabled() || !bf3_enabled() || c->transposed) return false;
-    ConvGeom g{}; geom_run(c, &g);
-    return viai_conv_stem_ok(g, cin_of(c), c->Cout, c->kh, c->kw, c->sh, c->sw, c->ph, c->pw);
 }
 
 // wp[co][r][s*4+ch] = w[co][ch][r][s], zero for s >= kw or ch >= Cin
@@ -307,395 +187,478 @@ int viai_geom_dgrad_class(const viai_conv2d* c, int a, int b, ConvGeom* g) {
     return nt;
 }
 
+// ---- routes ----------------------------------------------------------------------------------------------
+// One function per direction decides everything about a launch -- kernel, weight image, BatchNorm partial geometry, P16 mask -- from the
+// descriptor and the operand form.  The geometry is built once, into the argument block the launch will use; the family predicates (in the
+// files that own their tile constants) are each asked once.  The entry points, the pack functions and every query below read the route.
+//
+// The layer-level fields (layout of the fp32 / abs-max forms, stat_rows / tile_h / tile_w, p16, bf3, ksplit) do not depend on the form: the
+// fp32 and P16 forwards of one layer share one `stat` buffer and one weight image.  The one exception is `lin`: a P16 forward on the
+// linear-tile kernel writes its partials per 128 consecutive pixels, so layers reporting VIAI_P16_OK_FWD_LIN finalize with viai_bn_finalize_lin.
+
+static bool stem_layer(const viai_conv2d* c, const ConvGeom& g) {
+    return f16x2_enabled() && bf3_enabled() && !c->transposed && viai_conv_stem_ok(g, cin_of(c), c->Cout, c->kh, c->kw, c->sh, c->sw, c->ph, c->pw);
+}
+
+// the split-precision kernel of one launch (forward, or one parity class of a data gradient, as a.g says), in the order they are preferred
+static void pick_split_kernel(ConvRoute& r, const ConvArgs& a, bool halo, bool wide, bool lin, bool p16) {
+    const bool oc_ok = a.OC1 % 32 == 0 || a.OC1 == a.Cout;
+    if (halo) {
+        if (!oc_ok) return;
+        if (r.layout == WL_FRAG_F16 && viai_conv_halo16_ok(a.g, a.C1, a.C2, a.Cout)) {
+            r.kernel = (p16 && viai_conv_halo_c32_dma_ok(a)) ? CK_HALO_C32_DMA : CK_HALO_C32; r.family = "halo_c32_f16x2";
+        } else { r.kernel = CK_HALO; r.family = r.layout == WL_FRAG_F16 ? "halo_f16x2" : "halo_bf16x3"; }
+        return;
+    }
+    if (!oc_ok || (a.C2 > 0 && a.C1 % 32 != 0)) return;
+    if (!wl_frag(r.layout) && viai_bf3_sk_ok(a.M, a.Cout, a.C1, a.C2)) {
+        r.kernel = CK_IGEMM_SK; r.family = r.layout == WL_PLANAR_F16 ? "igemm_sk32x32_f16x2" : "igemm_sk32x32_bf16x3";
+    } else if (p16 && lin) { r.kernel = CK_LIN_DMA; r.family = "lin_dma_f16x2"; }
+    else if (wide) {
+        if (p16 && a.g.my == 2 && viai_conv_s2_dma_ok(a)) { r.kernel = CK_WIDE_DMA_S2; r.family = "halo_wide_s2_f16x2"; }
+        else if (p16 && a.g.my == 1 && viai_conv_s1_dma_ok(a)) { r.kernel = CK_WIDE_DMA_S1; r.family = "halo_wide256_f16x2"; }
+        else { r.kernel = CK_HALO_WIDE; r.family = viai_conv_halo_wide_family(a); }
+    } else if (!p16) { r.kernel = CK_IGEMM_BF3; r.family = viai_conv_igemm_bf3_family(r.layout, a.M, a.Cout); }      // only the patch-staged kernels stage P16 pieces
+}
+// the family tag comes from the route: the launchers launch what they are told and name nothing
+static int launch_conv_kernel(const ConvRoute& r, ConvArgs& a, hipStream_t st) {
+    if (r.kernel == CK_NONE) return (int)hipErrorInvalidValue;
+    viai_tag_kernel(r.family);
+    switch (r.kernel) {
+    case CK_STEM: return viai_conv_stem_fwd_launch(a, st);
+    case CK_IGEMM_F32: return viai_conv_igemm_launch(a, st);
+    case CK_DGRAD_S2: return viai_conv_dgrad_s2_bf3_launch(a, st);
+    case CK_DGRAD_S2_PATCH: return viai_conv_dgrad_s2_patch_launch(a, st);
+    case CK_HALO: return viai_conv_halo_bf3_launch(a, st);
+    case CK_HALO_C32: return viai_conv_halo_c32_launch(a, st);
+    case CK_HALO_C32_DMA: return viai_conv_halo_c32_dma_launch(a, st);
+    case CK_IGEMM_SK: return viai_conv_igemm_sk_launch(a, st);
+    case CK_IGEMM_BF3: return viai_conv_igemm_bf3_launch(a, st);
+    case CK_LIN_DMA: return viai_conv_lin_dma_launch(a, st);
+    case CK_HALO_WIDE: return viai_conv_halo_wide_launch(a, st);
+    case CK_WIDE_DMA_S1: return viai_conv_s1_dma_launch(a, st);
+    case CK_WIDE_DMA_S2: return viai_conv_s2_dma_launch(a, st);
+    default: return (int)hipErrorInvalidValue;
+    }
+}
+static void pick_f32_kernel(ConvRoute& r, const ConvArgs& a) {
+    if (!viai_conv_igemm_ok(a.C1, a.C2, a.Cout, a.OC1)) return;
+    r.kernel = CK_IGEMM_F32; r.family = viai_conv_igemm_family(a.M, a.Cout);
+}
+
+// forward.  Order: direct (Cin = 1 / Cout = 1), stem, fp32 igemm (VIAI_MATH=fp32 or Cin not in sixteens), then pick_split_kernel
+static ConvRoute route_fwd(const viai_conv2d* c, int form, ConvArgs& a) {
+    ConvRoute r{};
+    const int kind = kind_of(c);
+    const bool p16 = (form & 3) == VIAI_FORM_P16, f16 = f16x2_enabled();
+    r.layout = WL_F32; r.launches = 1; r.stat_rows = 128;
+    a.C1 = c->C1; a.C2 = c->C2; a.Cout = c->Cout; a.OC1 = c->Cout; a.in_p16 = p16;
+    if (kind == K_CIN1 || kind == K_COUT1) {
+        if (!p16) { r.kernel = CK_DIRECT; r.family = "direct"; }
+        return r;
+    }
+    if (kind == K_RUN) { geom_run(c, &a.g); a.C1 = 32; a.C2 = 0; }
+    else viai_geom_fwd(c, &a.g);
+    const ConvGeom& g = a.g;
+    a.M = g.N * g.OH * g.OW;
+    const long M = (long)g.N * g.OH * g.OW;
+    r.bf3 = kind == K_IGEMM && bf3_enabled() && cin_of(c) % 16 == 0;
+    if (!r.bf3) {
+        const bool stem = kind == K_RUN && stem_layer(c, g);
+        if (!stem) r.stat_rows = viai_igemm_tile_m(M, c->Cout);
+        r.f16 = stem;
+        if (stem && !p16) { r.kernel = CK_STEM; r.family = "stem_f16x2"; }
+        else if (!p16) pick_f32_kernel(r, a);
+        return r;
+    }
+    const bool halo = viai_conv_halo_ok(g, c->C1, c->C2, c->Cout);
+    const bool wide = f16 && viai_conv_halo_wide_ok(a), lin = f16 && viai_conv_lin_dma_geom_ok(a);
+    // weight image: fragment-major for the wide-tile, halo and linear-tile kernels, planar (staged in LDS) otherwise
+    r.layout = (halo || viai_bf3_frag_layout(M, c->Cout)) ? (f16 ? WL_FRAG_F16 : WL_FRAG_BF3) : (wide || lin) ? WL_FRAG_F16 : f16 ? WL_PLANAR_F16 : WL_PLANAR_BF3;
+    a.wfrag = r.layout;
+    if (!halo && !wide) r.stat_rows = (!wl_frag(r.layout) && viai_bf3_sk_ok(M, c->Cout, c->C1, c->C2)) ? 32 : viai_igemm_tile_m(M, c->Cout);
+    if (!halo && wide && c->sh == 2) r.stat_rows = 16 * viai_halo_s2_rows(g);          // stride-2 wide forward: 64-pixel tiles where it runs them
+    if (wide && (g.OH % 8 != 0 || g.OW % 16 != 0)) { r.tile_h = 8; r.tile_w = 16; }    // the wide halo kernel's 8 x 16 tiles, clipped at the map's edge
+    if (f16 && c->C2 == 0 && (halo || wide || lin)) r.p16 = VIAI_P16_OK_FWD_X | (lin ? VIAI_P16_OK_FWD_LIN : 0);
+    r.f16 = wl_f16(r.layout);
+    if (!p16 || r.p16) pick_split_kernel(r, a, halo, wide, lin, p16);
+    return r;
+}
+
+// data gradient (a: parity class (0, 0)).  Order: direct, fp32 igemm class by class, the fused stride-2 kernels, then pick_split_kernel class by class
+static ConvRoute route_dgrad(const viai_conv2d* c, int form, ConvArgs& a) {
+    ConvRoute r{};
+    const int kind = kind_of(c), Cin = cin_of(c);
+    const bool p16 = (form & 3) == VIAI_FORM_P16, amax = (form & 3) != VIAI_FORM_F32, f16 = f16x2_enabled();
+    r.layout = WL_F32;
+    if (kind == K_RUN) return r;                            // image inputs need no data gradient
+    if (kind != K_IGEMM) {
+        if (!amax) { r.kernel = CK_DIRECT; r.family = "direct"; r.launches = 1; r.ok = true; }
+        return r;
+    }
+    a.C1 = c->Cout; a.C2 = 0; a.Cout = Cin; a.OC1 = c->C1;        // produced tensor = dx, gathered tensor = dy: the channel roles swapped
+    a.in_p16 = p16;
+    const bool unit = c->sh == 1 && c->sw == 1;
+    bool halo = c->sw == 1 && (c->sh == 1 || (c->sh == 2 && f16 && !c->transposed));       // (the stride-(2, 1) layer: both row-parity classes on the halo kernel)
+    ConvArgs last = a;                                      // the last class that launches names the family
+    for (int a_ = 0; a_ < c->sh; ++a_)
+        for (int b_ = 0; b_ < c->sw; ++b_) {
+            ConvGeom tmp;
+            ConvGeom& g = (a_ == 0 && b_ == 0) ? a.g : tmp;
+            const int nt = viai_geom_dgrad_class(c, a_, b_, &g);
+            if (g.SH <= 0 || g.SW <= 0) continue;
+            if (nt == 0) { r.zero_fill = true; halo = false; continue; }         // a class with no valid tap (e.g. 1x1 stride 2) receives no gradient
+            halo = halo && viai_conv_halo_ok(g, c->Cout, 0, Cin);
+            r.launches += 1;
+            last.g = g;
+        }
+    last.M = last.g.N * last.g.SH * last.g.SW;
+    a.M = a.g.N * a.g.SH * a.g.SW;
+    r.bf3 = r.launches == 0 || (bf3_enabled() && c->Cout % 16 == 0);
+    r.f16 = f16 && r.bf3;
+    if (amax && !r.f16) return r;
+    if (!r.bf3) {
+        pick_f32_kernel(r, last);
+        r.ok = r.kernel != CK_NONE;
+        return r;
+    }
+    halo = halo && r.launches > 0;
+    const bool s2 = viai_dgrad_s2_ok(c);
+    const bool live0 = unit && r.launches == 1;
+    const bool wide = f16 && live0 && viai_conv_halo_wide_ok(a), lin = f16 && live0 && viai_conv_lin_dma_geom_ok(a);
+    const bool frag = halo || s2 || viai_bf3_frag_layout((long)c->N * ((c->IH + c->sh - 1) / c->sh) * ((c->IW + c->sw - 1) / c->sw), Cin);
+    r.layout = amax ? ((frag || wide || lin) ? WL_FRAG_F16 : WL_PLANAR_F16) : frag ? WL_FRAG_BF3 : WL_PLANAR_BF3;
+    a.wfrag = last.wfrag = r.layout;
+    if (f16 && (s2 || (unit && (halo || wide || lin)))) r.p16 = VIAI_P16_OK_DGRAD_DY;
+    if (p16 && !r.p16) return r;
+    if (s2) {                                               // all four parity classes in one launch
+        r.fused = r.ok = true; r.launches = 1;
+        if (amax && viai_dgrad_s2_patch_ok(c)) { r.kernel = CK_DGRAD_S2_PATCH; r.family = "dgrad_s2_patch_f16x2"; }
+        else { r.kernel = CK_DGRAD_S2; r.family = amax ? "dgrad_s2_f16x2" : "dgrad_s2_bf16x3"; }
+        return r;
+    }
+    r.halo = halo;
+    if (r.launches > 0) pick_split_kernel(r, last, halo, amax && wide, amax && lin, p16);       // (the patch-staged kernels are f16x2 only)
+    r.ok = r.launches == 0 || r.kernel != CK_NONE;
+    return r;
+}
+
+// weight gradient.  Order: direct, stem (f16x2 forms), patch (f16x2 forms), all-taps 32, bf3, fp32 MFMA
+static ConvRoute route_wgrad(const viai_conv2d* c, int form, WgradArgs& a) {
+    ConvRoute r{};
+    const int kind = kind_of(c), flags = (form & 3) == VIAI_FORM_P16 ? (form >> 2) : 0;
+    const bool amax = (form & 3) != VIAI_FORM_F32;
+    r.layout = WL_F32; r.ksplit = 1;
+    int oh, ow; viai_conv2d_out_hw(c, &oh, &ow);
+    const long M = (long)c->N * oh * ow;
+    a.C1 = c->C1; a.C2 = c->C2; a.Cout = c->Cout; a.M = (int)M;
+    a.dy_p16 = (flags & VIAI_P16_DY) ? 1 : 0; a.x_p16 = (flags & VIAI_P16_X) ? 1 : 0;
+    if (kind == K_CIN1 || kind == K_COUT1) {
+        if (!amax) { r.kernel = CK_DIRECT; r.family = "direct"; r.launches = 1; r.ok = true; }
+        return r;
+    }
+    if (kind == K_RUN) {
+        a.C1 = 32; a.C2 = 0;
+        geom_run(c, &a.g);
+        r.f16 = stem_layer(c, a.g);
+        if (amax && r.f16 && !flags) { r.kernel = CK_WGRAD_STEM; r.family = "wgrad_stem_f16x2"; r.ksplit = viai_conv_stem_wgrad_slabs(a.g); }
+        else if (!amax) {
+            r.ksplit = viai_wgrad_pick_ksplit(c->Cout, 32, c->kh, M);
+            if (viai_wgrad_mfma_ok(c->Cout, 32, 0)) { r.kernel = CK_WGRAD_MFMA; r.family = "wgrad_mfma_f32"; }
+        }
+        r.launches = r.ok = r.kernel != CK_NONE;
+        return r;
+    }
+    viai_geom_fwd(c, &a.g);
+    const bool split = f16x2_enabled() && bf3_enabled(), w32 = viai_wgrad32_ok(a.g, c->Cout, c->C1, c->C2), wbf3 = viai_wgrad_bf3_ok(c->Cout, c->C1, c->C2);
+    const int cfg = split ? viai_wgrad_patch_cfg(a.g, c->Cout, c->C1, c->C2, true) : 0;
+    r.ksplit = w32 ? viai_wgrad32_ksplit(M) : viai_wgrad_pick_ksplit(c->Cout, cin_of(c), c->kh * c->kw, M);
+    r.f16 = split && (wbf3 || cfg != 0);
+    if (cfg != 0) r.p16 = VIAI_P16_OK_WGRAD_DY | (c->C2 == 0 ? VIAI_P16_OK_WGRAD_X : 0);
+    if ((amax && !r.f16) || (flags && cfg == 0) || ((flags & VIAI_P16_X) && c->C2 > 0)) return r;
+    if (amax && cfg != 0) { r.kernel = CK_WGRAD_PATCH; r.family = viai_wgrad_patch_family(cfg); r.ksplit = viai_wgrad_patch_ksplit(a.g, c->Cout, c->C1, c->C2); }
+    else if (w32) { r.kernel = CK_WGRAD32; r.family = "wgrad32_all_taps_f32"; }
+    else if (bf3_enabled() && wbf3) { r.kernel = CK_WGRAD_BF3; r.family = amax ? "wgrad_bf3_f16x2" : "wgrad_bf3_bf16x3"; }
+    else if (viai_wgrad_mfma_ok(c->Cout, c->C1, c->C2)) { r.kernel = CK_WGRAD_MFMA; r.family = "wgrad_mfma_f32"; }
+    r.launches = r.ok = r.kernel != CK_NONE;
+    return r;
+}
+
+extern "C" int viai_conv2d_route(const viai_conv2d* c, int pass, int form, char* family, int cap) {
+    ConvRoute r{};
+    if (valid(c) && form >= 0 && pass >= 0 && pass <= 2) {
+        ConvArgs a{}; WgradArgs w{};
+        r = pass == 0 ? route_fwd(c, form, a) : pass == 1 ? route_dgrad(c, form, a) : route_wgrad(c, form, w);
+    }
+    copy_name(family, cap, r.kernel != CK_NONE ? r.family : "");
+    return r.kernel != CK_NONE ? r.launches : 0;
+}
+
+// ---- weight images -----------------------------------------------------------------------------------------
+// One image: forward form [Cout][T][Cin] (dgrad = false) or data-gradient form [Cin][T][Cout], in the layout of the route that reads it;
+// as a job of the batched pack when `job` is given, else packed now.  The streaming kernels share one fp32 image in both directions.
+static int pack_image(const viai_conv2d* c, bool dgrad, int layout, const float* w, float* wp, viai_pack_job* job, void* stream) {
+    const int T = c->kh * c->kw, Cin = cin_of(c), kind = kind_of(c);
+    if (kind != K_IGEMM) { dgrad = false; layout = WL_F32; }
+    const int n_out = dgrad ? Cin : c->Cout, k_in = dgrad ? c->Cout : Cin;
+    const long s_co = c->transposed ? T : (long)Cin * T, s_ci = c->transposed ? (long)c->Cout * T : T;      // torch strides of the output / input channel
+    const long s_no = kind == K_COUT1 ? 0 : dgrad ? s_ci : s_co, s_ki = dgrad ? s_co : s_ci;
+    if (job != nullptr) return viai_pack_job_bf3(w, wp, n_out, k_in, T, s_no, s_ki, layout, job);
+    if (layout == WL_F32) return viai_pack_weight(w, wp, n_out, k_in, T, s_no, s_ki, stream);
+    return viai_pack_weight_bf3(w, wp, n_out, k_in, T, s_no, s_ki, layout, (hipStream_t)stream);
+}
+
 extern "C" int viai_conv2d_pack_fwd(const viai_conv2d* c, const float* w, float* wp, void* stream) {
     if (!valid(c)) return (int)hipErrorInvalidValue;
-    const int T = c->kh * c->kw, Cin = cin_of(c);
-    switch (kind_of(c)) {
-    case K_CIN1:    // [Cout][T]: torch conv layout as is
-        return viai_pack_weight(w, wp, c->Cout, 1, T, c->transposed ? T : (long)T, c->transposed ? (long)c->Cout * T : T, stream);
-    case K_COUT1:   // wp[t][ci] == pack with n_out = 1 ... expressed as [1][T][Cin]
-        return viai_pack_weight(w, wp, 1, Cin, T, 0, T, stream);
-    case K_RUN: {
-        if (stem_f16(c)) return viai_conv_stem_pack(w, wp, Cin, (hipStream_t)stream);
+    ConvArgs a{};
+    const ConvRoute r = route_fwd(c, VIAI_FORM_F32, a);
+    if (kind_of(c) == K_RUN) {
+        if (r.kernel == CK_STEM) return viai_conv_stem_pack(w, wp, cin_of(c), (hipStream_t)stream);
         int total = c->Cout * c->kh * 32;
-        VIAI_LAUNCH(pack_run_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, wp, c->Cout, Cin, c->kh, c->kw);
+        VIAI_LAUNCH(pack_run_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, wp, c->Cout, cin_of(c), c->kh, c->kw);
         return viai_launch_status();
     }
-    default:
-        if (use_bf3_fwd(c)) {
-            const int M = frag_fwd(c);
-            if (c->transposed) return viai_pack_weight_bf3(w, wp, c->Cout, Cin, T, T, (long)c->Cout * T, M, (hipStream_t)stream);
-            return viai_pack_weight_bf3(w, wp, c->Cout, Cin, T, (long)Cin * T, T, M, (hipStream_t)stream);
-        }
-        if (c->transposed) return viai_pack_weight(w, wp, c->Cout, Cin, T, T, (long)c->Cout * T, stream);
-        return viai_pack_weight(w, wp, c->Cout, Cin, T, (long)Cin * T, T, stream);
-    }
+    return pack_image(c, false, r.layout, w, wp, nullptr, stream);
 }
 
 extern "C" int viai_conv2d_pack_dgrad(const viai_conv2d* c, const float* w, float* wp, void* stream) {
-    if (!valid(c)) return (int)hipErrorInvalidValue;
-    const int T = c->kh * c->kw, Cin = cin_of(c);
-    switch (kind_of(c)) {
-    case K_RUN: return (int)hipErrorInvalidValue;          // image inputs need no data gradient
-    case K_CIN1:
-    case K_COUT1:
-        return viai_conv2d_pack_fwd(c, w, wp, stream);     // the streaming kernels share one image
-    default:            // wp[ci][t][co]
-        if (use_bf3_dgrad(c)) {
-            const int M = frag_dgrad(c);
-            if (c->transposed) return viai_pack_weight_bf3(w, wp, Cin, c->Cout, T, (long)c->Cout * T, T, M, (hipStream_t)stream);
-            return viai_pack_weight_bf3(w, wp, Cin, c->Cout, T, T, (long)Cin * T, M, (hipStream_t)stream);
-        }
-        if (c->transposed) return viai_pack_weight(w, wp, Cin, c->Cout, T, (long)c->Cout * T, T, stream);
-        return viai_pack_weight(w, wp, Cin, c->Cout, T, T, (long)Cin * T, stream);
-    }
+    if (!valid(c) || kind_of(c) == K_RUN) return (int)hipErrorInvalidValue;          // image inputs need no data gradient
+    ConvArgs a{};
+    return pack_image(c, true, route_dgrad(c, VIAI_FORM_F32, a).layout, w, wp, nullptr, stream);
 }
 
-// Job descriptor of this layer's weight image for viai_pack_jobs_run; returns 1 for the one image kind that is not
-// batched (row-run mode of the image-input 7x7 conv: pack it with viai_conv2d_pack_fwd).
+// f16x2 data gradient: 1 if this layer has one (then pack with viai_conv2d_pack_dgrad_f16 and pass the abs-max of dy)
+extern "C" int viai_conv2d_dgrad_f16_ok(const viai_conv2d* c) {
+    if (!valid(c) || kind_of(c) != K_IGEMM) return 0;
+    ConvArgs a{};
+    return route_dgrad(c, VIAI_FORM_F32, a).f16 ? 1 : 0;
+}
+
+extern "C" int viai_conv2d_pack_dgrad_f16(const viai_conv2d* c, const float* w, float* wp, void* stream) {
+    if (!viai_conv2d_dgrad_f16_ok(c)) return (int)hipErrorInvalidValue;
+    ConvArgs a{};
+    return pack_image(c, true, route_dgrad(c, VIAI_FORM_AMAX, a).layout, w, wp, nullptr, stream);
+}
+
+// Job descriptor of this layer's weight image for viai_pack_jobs_run (dgrad: 0 forward image, 1 data-gradient image, 2 its f16x2 form);
+// returns 1 for the one image kind that is not batched (row-run mode of the image-input 7x7 conv: pack it with viai_conv2d_pack_fwd).
 extern "C" int viai_conv2d_pack_job(const viai_conv2d* c, int dgrad, const float* w, float* wp, viai_pack_job* job) {
     if (!valid(c) || job == nullptr) return (int)hipErrorInvalidValue;
-    const int T = c->kh * c->kw, Cin = cin_of(c);
-    switch (kind_of(c)) {                    // same cases as viai_conv2d_pack_fwd / _dgrad; frag = 2: fp32 [no][t][ki]
-    case K_RUN: return 1;
-    case K_CIN1: return viai_pack_job_bf3(w, wp, c->Cout, 1, T, c->transposed ? T : (long)T, c->transposed ? (long)c->Cout * T : T, 2, job);
-    case K_COUT1: return viai_pack_job_bf3(w, wp, 1, Cin, T, 0, T, 2, job);
-    default: break;
-    }
-    if (!dgrad) {
-        const int frag = use_bf3_fwd(c) ? frag_fwd(c) : 2;
-        if (c->transposed) return viai_pack_job_bf3(w, wp, c->Cout, Cin, T, T, (long)c->Cout * T, frag, job);
-        return viai_pack_job_bf3(w, wp, c->Cout, Cin, T, (long)Cin * T, T, frag, job);
-    }
-    if (dgrad == 2 && !dgrad_f16(c)) return (int)hipErrorInvalidValue;
-    const int frag = dgrad == 2 ? (frag_dgrad16(c) ? 3 : 4) : use_bf3_dgrad(c) ? (frag_dgrad(c) ? 1 : 0) : 2;
-    if (c->transposed) return viai_pack_job_bf3(w, wp, Cin, c->Cout, T, (long)c->Cout * T, T, frag, job);
-    return viai_pack_job_bf3(w, wp, Cin, c->Cout, T, T, (long)Cin * T, frag, job);
+    if (kind_of(c) == K_RUN) return 1;
+    ConvArgs a{};
+    if (!dgrad || kind_of(c) != K_IGEMM) return pack_image(c, false, route_fwd(c, VIAI_FORM_F32, a).layout, w, wp, job, nullptr);
+    if (dgrad == 2 && !viai_conv2d_dgrad_f16_ok(c)) return (int)hipErrorInvalidValue;
+    return pack_image(c, true, route_dgrad(c, dgrad == 2 ? VIAI_FORM_AMAX : VIAI_FORM_F32, a).layout, w, wp, job, nullptr);
 }
 
+// ---- forward -------------------------------------------------------------------------------------------------
 extern "C" int viai_conv2d_stat_geom(const viai_conv2d* c, int* nblk, int* rows_per_blk) {
     if (!valid(c)) return (int)hipErrorInvalidValue;
     if (kind_of(c) == K_CIN1) return viai_cin1_stat_geom(c, nblk, rows_per_blk);
+    ConvArgs a{};
+    const ConvRoute r = route_fwd(c, VIAI_FORM_F32, a);
     int oh, ow;
     viai_conv2d_out_hw(c, &oh, &ow);
-    long M = (long)c->N * oh * ow;
-    int bm = (kind_of(c) == K_COUT1 || stem_f16(c) || halo_fwd(c) || halo_wide_fwd(c)) ? 128 : sk_fwd(c) ? 32 : viai_igemm_tile_m(M, c->Cout);
-    if (kind_of(c) == K_IGEMM && !halo_fwd(c) && halo_wide_fwd(c) && c->sh == 2) {        // stride-2 wide halo forward: 64-pixel tiles where it runs them
-        ConvGeom g{}; viai_geom_fwd(c, &g);
-        bm = 16 * viai_halo_s2_rows(g);
-    }
-    *rows_per_blk = bm;
-    *nblk = (int)((M + bm - 1) / bm);
-    int th, tw;
-    if (viai_conv2d_stat_tiles(c, &th, &tw) == 0 && th > 0) *nblk = c->N * ((oh + th - 1) / th) * ((ow + tw - 1) / tw);
+    const long M = (long)c->N * oh * ow;
+    *rows_per_blk = r.stat_rows;
+    *nblk = r.tile_h > 0 ? c->N * ((oh + r.tile_h - 1) / r.tile_h) * ((ow + r.tile_w - 1) / r.tile_w) : (int)((M + r.stat_rows - 1) / r.stat_rows);
     return 0;
 }
 
 extern "C" int viai_conv2d_stat_tiles(const viai_conv2d* c, int* tile_h, int* tile_w) {
     if (!valid(c)) return (int)hipErrorInvalidValue;
-    *tile_h = *tile_w = 0;
-    if (kind_of(c) == K_CIN1 || kind_of(c) == K_COUT1 || !halo_wide_fwd(c)) return 0;
-    int oh, ow;
-    viai_conv2d_out_hw(c, &oh, &ow);
-    if (oh % 8 != 0 || ow % 16 != 0) { *tile_h = 8; *tile_w = 16; }       // the wide halo kernel's 8 x 16 tiles, clipped at the map's edge
+    ConvArgs a{};
+    const ConvRoute r = route_fwd(c, VIAI_FORM_F32, a);
+    *tile_h = r.tile_h; *tile_w = r.tile_w;
     return 0;
-}
-
-extern "C" int viai_conv2d_fwd(const viai_conv2d* c, const float* x, const float* x2, const float* wp,
-                               const float* bias, float* y, float* stat_part, int act, void* stream) {
-    return viai_conv2d_fwd_amax(c, x, x2, wp, bias, y, stat_part, act, nullptr, stream);
 }
 
 // 1 if the forward launch of this layer splits its activations into fp16 terms (then x_amax matters)
 extern "C" int viai_conv2d_fwd_f16_ok(const viai_conv2d* c) {
-    if (valid(c) && stem_f16(c)) return 1;
-    if (!valid(c) || kind_of(c) != K_IGEMM || !use_bf3_fwd(c)) return 0;
-    const int lay = frag_fwd(c);
-    return (lay == 3 || lay == 4) ? 1 : 0;
+    if (!valid(c)) return 0;
+    ConvArgs a{};
+    const ConvRoute r = route_fwd(c, VIAI_FORM_F32, a);
+    return r.f16 ? 1 : 0;
 }
 
 // x_amax: device float >= max |x| (and |x2|), or NULL.  The f16x2 kernels scale their activation operand by a power of two before the
 // split: from x_amax when it is given (any magnitude is then representable), by the static 16 otherwise (|x| beyond 4094 saturates)
 static int fwd_impl(const viai_conv2d* c, const float* x, const float* x2, const float* wp,
-                    const float* bias, float* y, float* stat_part, int act, const float* x_amax, void* stream, int p16);
-extern "C" int viai_conv2d_fwd_amax(const viai_conv2d* c, const float* x, const float* x2, const float* wp,
-                                    const float* bias, float* y, float* stat_part, int act, const float* x_amax, void* stream) {
-    return fwd_impl(c, x, x2, wp, bias, y, stat_part, act, x_amax, stream, 0);
-}
-static bool p16_fwd_ok(const viai_conv2d* c) {
-    return valid(c) && kind_of(c) == K_IGEMM && f16x2_enabled() && c->C2 == 0 && (halo_fwd(c) || halo_wide_fwd(c) || lin_fwd(c));
-}
-// (ABI 13) the forward with x pre-split (P16 planes, scale from *x_amax): layers with VIAI_P16_OK_FWD_X in viai_conv2d_p16_ok
-extern "C" int viai_conv2d_fwd_p16(const viai_conv2d* c, const float* x, const float* wp, const float* bias, float* y, float* stat_part,
-                                   int act, const float* x_amax, void* stream) {
-    if (!p16_fwd_ok(c) || x_amax == nullptr) return (int)hipErrorInvalidValue;
-    return fwd_impl(c, x, nullptr, wp, bias, y, stat_part, act, x_amax, stream, 1);
-}
-static int fwd_impl(const viai_conv2d* c, const float* x, const float* x2, const float* wp,
-                    const float* bias, float* y, float* stat_part, int act, const float* x_amax, void* stream, int p16) {
+                    const float* bias, float* y, float* stat_part, int act, const float* x_amax, void* stream, int form) {
     if (!valid(c) || (c->C2 > 0) != (x2 != nullptr)) return (int)hipErrorInvalidValue;
     if (stat_part != nullptr && act != VIAI_ACT_NONE) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     viai_tag_reset();
-    switch (kind_of(c)) {
-    case K_CIN1: viai_tag_kernel("direct"); return viai_cin1_fwd(c, x, wp, bias, y, stat_part, act, st);
-    case K_COUT1:
-        if (stat_part) return (int)hipErrorInvalidValue;
-        viai_tag_kernel("direct");
-        return viai_cout1_fwd(c, x, wp, bias, y, act, st);
-    default: break;
-    }
     ConvArgs a{};
+    const ConvRoute r = route_fwd(c, form, a);
     a.in = x; a.in2 = x2; a.wp = wp; a.bias = bias; a.out = y; a.out2 = nullptr; a.stat = stat_part;
-    a.C1 = c->C1; a.C2 = c->C2; a.Cout = c->Cout; a.OC1 = c->Cout;
     a.act = act; a.slope = 0.2f;
-    a.in_p16 = p16;
-    if (kind_of(c) == K_RUN) { geom_run(c, &a.g); a.C1 = 32; a.C2 = 0; }
-    else viai_geom_fwd(c, &a.g);
-    a.M = a.g.N * a.g.OH * a.g.OW;
-    if (stem_f16(c)) { a.amax = x_amax; return viai_conv_stem_fwd_launch(a, st); }
-    if (use_bf3_fwd(c)) {
-        a.wfrag = frag_fwd(c);
-        if (a.wfrag == 3 || a.wfrag == 4) a.amax = x_amax;            // f16x2 weight image = f16x2 kernel
-        if (halo_fwd(c)) return viai_conv_halo_bf3_launch(a, st);
-        a.sk = sk_fwd(c);
-        return viai_conv_igemm_bf3_launch(a, st);
-    }
-    return viai_conv_igemm_launch(a, st);
+    if (r.f16) a.amax = x_amax;                              // f16x2 weight image = f16x2 kernel
+    if (r.kernel != CK_DIRECT) return launch_conv_kernel(r, a, st);
+    if (kind_of(c) == K_COUT1 && stat_part) return (int)hipErrorInvalidValue;
+    viai_tag_kernel(r.family);
+    return kind_of(c) == K_CIN1 ? viai_cin1_fwd(c, x, wp, bias, y, stat_part, act, st) : viai_cout1_fwd(c, x, wp, bias, y, act, st);
+}
+extern "C" int viai_conv2d_fwd(const viai_conv2d* c, const float* x, const float* x2, const float* wp,
+                               const float* bias, float* y, float* stat_part, int act, void* stream) {
+    return fwd_impl(c, x, x2, wp, bias, y, stat_part, act, nullptr, stream, VIAI_FORM_F32);
+}
+extern "C" int viai_conv2d_fwd_amax(const viai_conv2d* c, const float* x, const float* x2, const float* wp,
+                                    const float* bias, float* y, float* stat_part, int act, const float* x_amax, void* stream) {
+    return fwd_impl(c, x, x2, wp, bias, y, stat_part, act, x_amax, stream, x_amax != nullptr ? VIAI_FORM_AMAX : VIAI_FORM_F32);
+}
+// (ABI 13) the forward with x pre-split (P16 planes, scale from *x_amax): layers with VIAI_P16_OK_FWD_X in viai_conv2d_p16_ok
+extern "C" int viai_conv2d_fwd_p16(const viai_conv2d* c, const float* x, const float* wp, const float* bias, float* y, float* stat_part,
+                                   int act, const float* x_amax, void* stream) {
+    if (x_amax == nullptr) return (int)hipErrorInvalidValue;
+    return fwd_impl(c, x, nullptr, wp, bias, y, stat_part, act, x_amax, stream, VIAI_FORM_P16);
 }
 
-static int dgrad_impl(const viai_conv2d* c, const float* dy, const float* wp, float* dx, float* dx2, const float* amax, void* stream, int p16 = 0);
-
-extern "C" int viai_conv2d_dgrad(const viai_conv2d* c, const float* dy, const float* wp, float* dx, float* dx2, void* stream) {
-    return dgrad_impl(c, dy, wp, dx, dx2, nullptr, stream);
-}
-
-// f16x2 data gradient: 1 if this layer has one (then pack with viai_conv2d_pack_dgrad_f16 and pass the abs-max of dy)
-extern "C" int viai_conv2d_dgrad_f16_ok(const viai_conv2d* c) { return (valid(c) && kind_of(c) == K_IGEMM && dgrad_f16(c)) ? 1 : 0; }
-
-extern "C" int viai_conv2d_pack_dgrad_f16(const viai_conv2d* c, const float* w, float* wp, void* stream) {
-    if (!viai_conv2d_dgrad_f16_ok(c)) return (int)hipErrorInvalidValue;
-    const int T = c->kh * c->kw, Cin = cin_of(c);
-    const int lay = frag_dgrad16(c) ? 3 : 4;
-    if (c->transposed) return viai_pack_weight_bf3(w, wp, Cin, c->Cout, T, (long)c->Cout * T, T, lay, (hipStream_t)stream);
-    return viai_pack_weight_bf3(w, wp, Cin, c->Cout, T, T, (long)Cin * T, lay, (hipStream_t)stream);
-}
-
-// dy_amax: device float holding max |dy| (viai_bn_act_bwd_amax): the f16x2 operand scale is derived from it on the device
-extern "C" int viai_conv2d_dgrad_f16(const viai_conv2d* c, const float* dy, const float* wp, float* dx, float* dx2,
-                                     const float* dy_amax, void* stream) {
-    if (!viai_conv2d_dgrad_f16_ok(c) || dy_amax == nullptr) return (int)hipErrorInvalidValue;
-    return dgrad_impl(c, dy, wp, dx, dx2, dy_amax, stream);
-}
-
-// the patch-staged stride-2 data gradient (conv_dgrad_s2_bf3.hip) takes this layer: base lattice a multiple of 8 x 16
-static bool s2_patch_dgrad(const viai_conv2d* c) {
-    if (!s2_dgrad(c)) return false;
-    int oh, ow; viai_conv2d_out_hw(c, &oh, &ow);
-    return oh % 8 == 0 && ow % 16 == 0 && c->IH == 2 * oh && c->IW == 2 * ow && c->Cout % 32 == 0;
-}
-static bool p16_dgrad_ok(const viai_conv2d* c) {
-    if (!valid(c) || kind_of(c) != K_IGEMM || !dgrad_f16(c)) return false;
-    if (s2_dgrad(c)) return s2_patch_dgrad(c) || c->Cout % 32 == 0;          // (round 5: the gather kernel of the fused classes stages pieces too)
-    return c->sh == 1 && c->sw == 1 && (halo_dgrad(c) || halo_wide_dgrad(c) || lin_dgrad(c));
-}
-// (ABI 13) viai_conv2d_dgrad_f16 with dy pre-split (P16 planes, scale from *dy_amax): layers with VIAI_P16_OK_DGRAD_DY
-extern "C" int viai_conv2d_dgrad_f16_p16(const viai_conv2d* c, const float* dy, const float* wp, float* dx, float* dx2,
-                                         const float* dy_amax, void* stream) {
-    if (!p16_dgrad_ok(c) || dy_amax == nullptr) return (int)hipErrorInvalidValue;
-    return dgrad_impl(c, dy, wp, dx, dx2, dy_amax, stream, 1);
-}
-
-static int dgrad_impl(const viai_conv2d* c, const float* dy, const float* wp, float* dx, float* dx2, const float* amax, void* stream, int p16) {
+// ---- data gradient -------------------------------------------------------------------------------------------
+static int dgrad_impl(const viai_conv2d* c, const float* dy, const float* wp, float* dx, float* dx2, const float* amax, void* stream, int form) {
     if (!valid(c) || (c->C2 > 0) != (dx2 != nullptr)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     viai_tag_reset();
-    switch (kind_of(c)) {
-    case K_CIN1: viai_tag_kernel("direct"); return viai_cin1_dgrad(c, dy, wp, dx, st);
-    case K_COUT1: viai_tag_kernel("direct"); return viai_cout1_dgrad(c, dy, wp, dx, st);
-    case K_RUN: return (int)hipErrorInvalidValue;
-    default: break;
+    ConvArgs a{};
+    const ConvRoute r = route_dgrad(c, form, a);
+    if (!r.ok) return (int)hipErrorInvalidValue;
+    if (r.kernel == CK_DIRECT) {
+        viai_tag_kernel(r.family);
+        return kind_of(c) == K_CIN1 ? viai_cin1_dgrad(c, dy, wp, dx, st) : viai_cout1_dgrad(c, dy, wp, dx, st);
     }
-    {   // a parity class with no valid tap (e.g. 1x1 stride 2) receives no gradient: zero-fill first
-        bool empty = false;
-        for (int a_ = 0; a_ < c->sh && !empty; ++a_)
-            for (int b_ = 0; b_ < c->sw; ++b_) { ConvGeom g; if (viai_geom_dgrad_class(c, a_, b_, &g) == 0 && g.SH > 0 && g.SW > 0) { empty = true; break; } }
-        if (empty) {
-            size_t px = (size_t)c->N * c->IH * c->IW;
-            if (hipMemsetAsync(dx, 0, px * c->C1 * sizeof(float), st) != hipSuccess) return (int)hipErrorInvalidValue;
-            if (dx2 && hipMemsetAsync(dx2, 0, px * c->C2 * sizeof(float), st) != hipSuccess) return (int)hipErrorInvalidValue;
-        }
+    if (r.zero_fill) {
+        size_t px = (size_t)c->N * c->IH * c->IW;
+        if (hipMemsetAsync(dx, 0, px * c->C1 * sizeof(float), st) != hipSuccess) return (int)hipErrorInvalidValue;
+        if (dx2 && hipMemsetAsync(dx2, 0, px * c->C2 * sizeof(float), st) != hipSuccess) return (int)hipErrorInvalidValue;
     }
-    const bool bf3 = use_bf3_dgrad(c);
-    if (s2_dgrad(c)) {                                     // all four parity classes in one launch
-        ConvArgs a{};
-        a.in = dy; a.wp = wp; a.out = dx; a.out2 = dx2;
-        a.C1 = c->Cout; a.C2 = 0; a.Cout = cin_of(c); a.OC1 = c->C1;
+    a.in = dy; a.wp = wp; a.out = dx; a.out2 = dx2;
+    a.act = VIAI_ACT_NONE;
+    a.amax = amax;
+    if (r.fused) {
         int oh, ow; viai_conv2d_out_hw(c, &oh, &ow);
+        a.g = ConvGeom{};
         a.g.N = c->N; a.g.IH = oh; a.g.IW = ow; a.g.OH = c->IH; a.g.OW = c->IW;
         a.M = c->N * (c->IH / 2) * (c->IW / 2);
-        a.wfrag = amax != nullptr ? 3 : 1;
-        a.amax = amax;
-        a.in_p16 = p16;
-        return viai_conv_dgrad_s2_bf3_launch(a, st);
+        return launch_conv_kernel(r, a, st);
     }
     for (int a_ = 0; a_ < c->sh; ++a_)
         for (int b_ = 0; b_ < c->sw; ++b_) {
-            ConvArgs a{};
-            a.in = dy; a.in2 = nullptr; a.wp = wp; a.bias = nullptr; a.out = dx; a.out2 = dx2; a.stat = nullptr;
-            a.C1 = c->Cout; a.C2 = 0; a.Cout = cin_of(c); a.OC1 = c->C1;
-            a.act = VIAI_ACT_NONE; a.slope = 0.f;
-            a.in_p16 = p16;
-            int nt = viai_geom_dgrad_class(c, a_, b_, &a.g);
-            if (a.g.SH <= 0 || a.g.SW <= 0) continue;
-            if (nt == 0) continue;                            // zero-filled above
+            // (one argument block for all classes: tap slots beyond ntaps keep the previous class's values, which no kernel reads)
+            if (a_ + b_ > 0 && viai_geom_dgrad_class(c, a_, b_, &a.g) == 0) continue;        // (class (0, 0) is in a.g already; tapless: zero-filled above)
+            if (a.g.SH <= 0 || a.g.SW <= 0 || a.g.ntaps == 0) continue;
             a.M = a.g.N * a.g.SH * a.g.SW;
-            a.wfrag = bf3 && frag_dgrad(c);
-            if (amax != nullptr) { a.wfrag = frag_dgrad16(c) ? 3 : 4; a.amax = amax; }       // f16x2 weights + dynamic operand scale
-            a.sk = bf3 && (a.wfrag == 0 || a.wfrag == 4) && viai_bf3_sk_ok(a.M, a.Cout, a.C1, 0);
-            int e = (bf3 && halo_dgrad(c)) ? viai_conv_halo_bf3_launch(a, st) : bf3 ? viai_conv_igemm_bf3_launch(a, st) : viai_conv_igemm_launch(a, st);
+            ConvRoute rc = r;                                 // strided: the tile instance follows the rows of the class
+            if (c->sh * c->sw > 1) { rc.kernel = CK_NONE; if (r.bf3) pick_split_kernel(rc, a, r.halo, false, false, false); else pick_f32_kernel(rc, a); }
+            int e = launch_conv_kernel(rc, a, st);
             if (e) return e;
         }
     return 0;
 }
-
-// weight-gradient split-K of the igemm-class layers: the all-taps 32-channel kernel has its own rule (one slab per block)
-static bool wgrad32(const viai_conv2d* c) {
-    if (kind_of(c) != K_IGEMM) return false;
-    ConvGeom g{}; viai_geom_fwd(c, &g);
-    return viai_wgrad32_ok(g, c->Cout, c->C1, c->C2);
+extern "C" int viai_conv2d_dgrad(const viai_conv2d* c, const float* dy, const float* wp, float* dx, float* dx2, void* stream) {
+    return dgrad_impl(c, dy, wp, dx, dx2, nullptr, stream, VIAI_FORM_F32);
 }
-static int wgrad_ksplit(const viai_conv2d* c, long M) {
-    if (wgrad32(c)) return viai_wgrad32_ksplit(M);
-    return viai_wgrad_pick_ksplit(c->Cout, cin_of(c), c->kh * c->kw, M);
+// dy_amax: device float holding max |dy| (viai_bn_act_bwd_amax): the f16x2 operand scale is derived from it on the device
+extern "C" int viai_conv2d_dgrad_f16(const viai_conv2d* c, const float* dy, const float* wp, float* dx, float* dx2,
+                                     const float* dy_amax, void* stream) {
+    if (dy_amax == nullptr) return (int)hipErrorInvalidValue;
+    return dgrad_impl(c, dy, wp, dx, dx2, dy_amax, stream, VIAI_FORM_AMAX);
 }
-// the all-taps patch kernel (f16x2 launches of the stride-1 3 x 3 layers with >= 128 x 64 channels)
-static bool wgrad_patch(const viai_conv2d* c, bool shape_only = false) {
-    if (kind_of(c) != K_IGEMM || !f16x2_enabled() || !bf3_enabled()) return false;
-    ConvGeom g{}; viai_geom_fwd(c, &g);
-    return shape_only ? viai_wgrad_patch_shape_ok(g, c->Cout, c->C1, c->C2) : viai_wgrad_patch_ok(g, c->Cout, c->C1, c->C2);
+// (ABI 13) viai_conv2d_dgrad_f16 with dy pre-split (P16 planes, scale from *dy_amax): layers with VIAI_P16_OK_DGRAD_DY
+extern "C" int viai_conv2d_dgrad_f16_p16(const viai_conv2d* c, const float* dy, const float* wp, float* dx, float* dx2,
+                                         const float* dy_amax, void* stream) {
+    if (dy_amax == nullptr) return (int)hipErrorInvalidValue;
+    return dgrad_impl(c, dy, wp, dx, dx2, dy_amax, stream, VIAI_FORM_P16);
 }
 
+// ---- weight gradient -----------------------------------------------------------------------------------------
 extern "C" size_t viai_conv2d_wgrad_ws_bytes(const viai_conv2d* c) {
     if (!valid(c)) return 0;
-    size_t fl;
+    WgradArgs a{};
+    const ConvRoute r = route_wgrad(c, VIAI_FORM_F32, a);
+    size_t ks = r.ksplit, fl;
     switch (kind_of(c)) {
     case K_CIN1: fl = viai_cin1_wgrad_ws_floats(c); break;
     case K_COUT1: fl = viai_cout1_wgrad_ws_floats(c); break;
-    case K_RUN: {
-        int oh, ow; viai_conv2d_out_hw(c, &oh, &ow);
-        int ks = viai_wgrad_pick_ksplit(c->Cout, 32, c->kh, (long)c->N * oh * ow);
-        if (stem_f16(c)) { ConvGeom g{}; geom_run(c, &g); const int kz = viai_conv_stem_wgrad_slabs(g); if (kz > ks) ks = kz; }
-        fl = (size_t)ks * viai_conv2d_packed_floats(c); break;
-    }
-    default: {
-        int oh, ow; viai_conv2d_out_hw(c, &oh, &ow);
-        long M = (long)c->N * oh * ow;
-        int ks = wgrad_ksplit(c, M);
-        if (wgrad_patch(c, true)) {                            // workspace covers every form the layer can take, whatever the switches say
-            ConvGeom g{}; viai_geom_fwd(c, &g);
-            int kp = viai_wgrad_patch_ksplit(g, c->Cout, c->C1, c->C2);
+    case K_RUN:
+        if (r.f16 && (size_t)viai_conv_stem_wgrad_slabs(a.g) > ks) ks = viai_conv_stem_wgrad_slabs(a.g);
+        fl = ks * viai_conv2d_packed_floats(c); break;
+    default:                                                  // the workspace covers every form the layer can take, whatever VIAI_WGRAD_PATCH_S2 says
+        if (f16x2_enabled() && bf3_enabled() && viai_wgrad_patch_cfg(a.g, c->Cout, c->C1, c->C2, false) != 0) {
+            const size_t kp = viai_wgrad_patch_ksplit(a.g, c->Cout, c->C1, c->C2);
             if (kp > ks) ks = kp;
         }
-        fl = (size_t)ks * viai_conv2d_packed_floats(c);
-    } }
+        fl = ks * viai_conv2d_packed_floats(c);
+    }
     // + column-sum partials for the bias gradient
-    int oh, ow; viai_conv2d_out_hw(c, &oh, &ow);
-    fl += (size_t)viai_colsum_blocks((long)c->N * oh * ow, c->Cout) * c->Cout;
+    fl += (size_t)viai_colsum_blocks((long)a.M, c->Cout) * c->Cout;
     return fl * sizeof(float);
 }
 
-static int wgrad_impl(const viai_conv2d* c, const float* x, const float* x2, const float* dy,
-                      float* ws, float* dw, float* db, int accumulate, const float* amax, const float* xmax, void* stream, int p16 = 0);
-
-extern "C" int viai_conv2d_wgrad(const viai_conv2d* c, const float* x, const float* x2, const float* dy,
-                                 float* ws, float* dw, float* db, int accumulate, void* stream) {
-    return wgrad_impl(c, x, x2, dy, ws, dw, db, accumulate, nullptr, nullptr, stream);
-}
-
-// f16x2 weight gradient (layers on the bf16x3 wgrad kernel): dy scaled on the device from dy_amax = max |dy|, x by the
-// static activation scale; 1 from viai_conv2d_wgrad_f16_ok if the layer has this form
+// f16x2 weight gradient: dy scaled on the device from dy_amax = max |dy|, x by the static activation scale or from x_amax; the layers of the
+// f16x2 wgrad_bf3 kernel (> 32 channels on both sides), every layer an instance of the patch kernel takes, and the stem
 extern "C" int viai_conv2d_wgrad_f16_ok(const viai_conv2d* c) {
-    // the layers of the f16x2 wgrad_bf3 kernel (> 32 channels on both sides) and every layer an instance of the patch kernel takes
-    if (valid(c) && stem_f16(c)) return 1;
-    return (valid(c) && kind_of(c) == K_IGEMM && f16x2_enabled() && bf3_enabled() && (viai_wgrad_bf3_ok(c->Cout, c->C1, c->C2) || wgrad_patch(c))) ? 1 : 0;
-}
-extern "C" int viai_conv2d_wgrad_f16(const viai_conv2d* c, const float* x, const float* x2, const float* dy,
-                                     float* ws, float* dw, float* db, int accumulate, const float* dy_amax, const float* x_amax, void* stream) {
-    if (!viai_conv2d_wgrad_f16_ok(c) || dy_amax == nullptr) return (int)hipErrorInvalidValue;
-    return wgrad_impl(c, x, x2, dy, ws, dw, db, accumulate, dy_amax, x_amax, stream);
+    if (!valid(c)) return 0;
+    WgradArgs a{};
+    return route_wgrad(c, VIAI_FORM_F32, a).f16 ? 1 : 0;
 }
 
 // (ABI 13) which operands of this layer's f16x2 kernels may arrive pre-split (P16 planes, csrc/viai_bf3.h): a mask of VIAI_P16_OK_*
 extern "C" int viai_conv2d_p16_ok(const viai_conv2d* c) {
     if (!valid(c) || kind_of(c) != K_IGEMM || !f16x2_enabled() || !bf3_enabled()) return 0;
-    int m = 0;
-    if (wgrad_patch(c)) { m |= VIAI_P16_OK_WGRAD_DY; if (c->C2 == 0) m |= VIAI_P16_OK_WGRAD_X; }
-    if (p16_fwd_ok(c)) m |= VIAI_P16_OK_FWD_X;
-    if (p16_fwd_ok(c) && lin_fwd(c)) m |= VIAI_P16_OK_FWD_LIN;
-    if (p16_dgrad_ok(c)) m |= VIAI_P16_OK_DGRAD_DY;
-    return m;
-}
-extern "C" int viai_conv2d_wgrad_f16_p16(const viai_conv2d* c, const float* x, const float* x2, const float* dy,
-                                         float* ws, float* dw, float* db, int accumulate, const float* dy_amax, const float* x_amax, int flags, void* stream) {
-    if (!viai_conv2d_wgrad_f16_ok(c) || dy_amax == nullptr) return (int)hipErrorInvalidValue;
-    return wgrad_impl(c, x, x2, dy, ws, dw, db, accumulate, dy_amax, x_amax, stream, flags);
+    ConvArgs a{}, b{}; WgradArgs w{};
+    return route_wgrad(c, VIAI_FORM_F32, w).p16 | route_fwd(c, VIAI_FORM_F32, a).p16 | route_dgrad(c, VIAI_FORM_F32, b).p16;
 }
 
 static int wgrad_impl(const viai_conv2d* c, const float* x, const float* x2, const float* dy,
-                      float* ws, float* dw, float* db, int accumulate, const float* amax, const float* xmax, void* stream, int p16) {
+                      float* ws, float* dw, float* db, int accumulate, const float* amax, const float* xmax, void* stream, int form) {
     if (!valid(c) || (c->C2 > 0) != (x2 != nullptr)) return (int)hipErrorInvalidValue;
-    if (p16 != 0 && (kind_of(c) != K_IGEMM || amax == nullptr || !wgrad_patch(c) || ((p16 & VIAI_P16_DY) && db != nullptr)
-                     || ((p16 & VIAI_P16_X) && (x2 != nullptr || xmax == nullptr)))) return (int)hipErrorInvalidValue;
+    const int flags = (form & 3) == VIAI_FORM_P16 ? (form >> 2) : 0;
+    if (((flags & VIAI_P16_DY) && db != nullptr) || ((flags & VIAI_P16_X) && xmax == nullptr)) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
-    int oh, ow; viai_conv2d_out_hw(c, &oh, &ow);
-    const long M = (long)c->N * oh * ow;
-    const int T = c->kh * c->kw, Cin = cin_of(c);
-    int e = 0;
-    size_t used = 0;
     viai_tag_reset();
-    if (kind_of(c) == K_CIN1 || kind_of(c) == K_COUT1) viai_tag_kernel("direct");
-    switch (kind_of(c)) {
-    case K_CIN1: e = viai_cin1_wgrad(c, x, dy, ws, dw, accumulate, st); used = viai_cin1_wgrad_ws_floats(c); break;
-    case K_COUT1: e = viai_cout1_wgrad(c, x, dy, ws, dw, accumulate, st); used = viai_cout1_wgrad_ws_floats(c); break;
-    case K_RUN: {
-        WgradArgs a{};
-        a.x = x; a.x2 = nullptr; a.dy = dy; a.ws = ws; a.C1 = 32; a.C2 = 0; a.Cout = c->Cout; a.M = (int)M;
-        geom_run(c, &a.g);
-        if (amax != nullptr && stem_f16(c)) {                 // f16x2 launch (viai_conv2d_wgrad_f16): conv_stem.hip, slabs + reduce in one call
-            a.amax = amax; a.xmax = xmax;
-            used = (size_t)viai_conv_stem_wgrad_slabs(a.g) * viai_conv2d_packed_floats(c);
-            e = viai_conv_stem_wgrad_launch(a, Cin, dw, accumulate, st);
-            break;
-        }
-        int ks = viai_wgrad_pick_ksplit(c->Cout, 32, c->kh, M);
-        used = (size_t)ks * viai_conv2d_packed_floats(c);
-        e = viai_wgrad_mfma_launch(a, ks, st);
-        if (e) return e;
-        int total = c->Cout * Cin * T;
-        VIAI_LAUNCH(wgrad_reduce_run_kernel, dim3((total + 255) / 256), dim3(256), 0, st, ws, dw, ks, c->Cout, Cin, c->kh, c->kw, accumulate);
-        e = viai_launch_status();
+    WgradArgs a{};
+    const ConvRoute r = route_wgrad(c, form, a);
+    if (!r.ok) return (int)hipErrorInvalidValue;
+    const int T = c->kh * c->kw, Cin = cin_of(c);
+    a.x = x; a.x2 = kind_of(c) == K_RUN ? nullptr : x2; a.dy = dy; a.ws = ws; a.amax = amax; a.xmax = xmax;
+    size_t used = (size_t)r.ksplit * viai_conv2d_packed_floats(c);
+    int e = 0;
+    viai_tag_kernel(r.family);
+    switch (r.kernel) {
+    case CK_DIRECT:
+        if (kind_of(c) == K_CIN1) { e = viai_cin1_wgrad(c, x, dy, ws, dw, accumulate, st); used = viai_cin1_wgrad_ws_floats(c); }
+        else { e = viai_cout1_wgrad(c, x, dy, ws, dw, accumulate, st); used = viai_cout1_wgrad_ws_floats(c); }
         break;
+    case CK_WGRAD_STEM: e = viai_conv_stem_wgrad_launch(a, Cin, dw, accumulate, st); break;       // slabs + reduce in one call
+    case CK_WGRAD_PATCH: e = viai_wgrad_patch_launch(a, st); break;
+    case CK_WGRAD32: e = viai_wgrad32_launch(a, r.ksplit, st); break;
+    case CK_WGRAD_BF3: e = viai_wgrad_bf3_launch(a, r.ksplit, st); break;
+    default: e = viai_wgrad_mfma_launch(a, r.ksplit, st);
     }
-    default: {
-        WgradArgs a{};
-        a.x = x; a.x2 = x2; a.dy = dy; a.ws = ws; a.C1 = c->C1; a.C2 = c->C2; a.Cout = c->Cout; a.M = (int)M;
-        a.amax = amax;
-        a.xmax = xmax;
-        a.dy_p16 = (p16 & VIAI_P16_DY) ? 1 : 0; a.x_p16 = (p16 & VIAI_P16_X) ? 1 : 0;
-        viai_geom_fwd(c, &a.g);
-        int ks = wgrad_ksplit(c, M);
-        const bool patch = amax != nullptr && wgrad_patch(c);
-        if (patch) ks = viai_wgrad_patch_ksplit(a.g, c->Cout, c->C1, c->C2);
-        used = (size_t)ks * viai_conv2d_packed_floats(c);
-        e = patch ? viai_wgrad_patch_launch(a, st)
-          : wgrad32(c) ? viai_wgrad32_launch(a, ks, st)
-          : (bf3_enabled() && viai_wgrad_bf3_ok(c->Cout, c->C1, c->C2)) ? viai_wgrad_bf3_launch(a, ks, st) : viai_wgrad_mfma_launch(a, ks, st);
-        if (e) return e;
-        if (c->transposed) e = viai_wgrad_reduce(ws, dw, ks, T, c->Cout, Cin, T, (long)c->Cout * T, accumulate, st);
-        else e = viai_wgrad_reduce(ws, dw, ks, T, c->Cout, Cin, (long)Cin * T, T, accumulate, st);
-    } }
     if (e) return e;
-    if (db != nullptr) e = viai_colsum(dy, M, c->Cout, ws + used, db, accumulate, stream);
+    if (kind_of(c) == K_RUN && r.kernel == CK_WGRAD_MFMA) {
+        int total = c->Cout * Cin * T;
+        VIAI_LAUNCH(wgrad_reduce_run_kernel, dim3((total + 255) / 256), dim3(256), 0, st, ws, dw, r.ksplit, c->Cout, Cin, c->kh, c->kw, accumulate);
+        e = viai_launch_status();
+    } else if (kind_of(c) == K_IGEMM) {
+        if (c->transposed) e = viai_wgrad_reduce(ws, dw, r.ksplit, T, c->Cout, Cin, T, (long)c->Cout * T, accumulate, st);
+        else e = viai_wgrad_reduce(ws, dw, r.ksplit, T, c->Cout, Cin, (long)Cin * T, T, accumulate, st);
+    }
+    if (e) return e;
+    if (db != nullptr) e = viai_colsum(dy, a.M, c->Cout, ws + used, db, accumulate, stream);
     return e;
+}
+extern "C" int viai_conv2d_wgrad(const viai_conv2d* c, const float* x, const float* x2, const float* dy,
+                                 float* ws, float* dw, float* db, int accumulate, void* stream) {
+    return wgrad_impl(c, x, x2, dy, ws, dw, db, accumulate, nullptr, nullptr, stream, VIAI_FORM_F32);
+}
+extern "C" int viai_conv2d_wgrad_f16(const viai_conv2d* c, const float* x, const float* x2, const float* dy,
+                                     float* ws, float* dw, float* db, int accumulate, const float* dy_amax, const float* x_amax, void* stream) {
+    if (dy_amax == nullptr) return (int)hipErrorInvalidValue;
+    return wgrad_impl(c, x, x2, dy, ws, dw, db, accumulate, dy_amax, x_amax, stream, VIAI_FORM_AMAX);
+}
+extern "C" int viai_conv2d_wgrad_f16_p16(const viai_conv2d* c, const float* x, const float* x2, const float* dy,
+                                         float* ws, float* dw, float* db, int accumulate, const float* dy_amax, const float* x_amax, int flags, void* stream) {
+    if (dy_amax == nullptr || flags < 0) return (int)hipErrorInvalidValue;
+    return wgrad_impl(c, x, x2, dy, ws, dw, db, accumulate, dy_amax, x_amax, stream, flags ? (VIAI_FORM_P16 | (flags << 2)) : VIAI_FORM_AMAX);
 }

@@ -396,8 +396,30 @@ bool viai_dgrad_s2_ok(const viai_conv2d* c) {
     return blocks >= (tiles ? small : 256);
 }
 
+// the patch-staged kernel (f16x2 launches) takes the layer: base lattice a multiple of 8 x 16
+bool viai_dgrad_s2_patch_ok(const viai_conv2d* c) {
+    int oh, ow; viai_conv2d_out_hw(c, &oh, &ow);
+    return viai_dgrad_s2_ok(c) && oh % 8 == 0 && ow % 16 == 0 && c->IH == 2 * oh && c->IW == 2 * ow && c->Cout % 32 == 0;
+}
+
+// a.g: N, IH/IW = dy extent, OH/OW = dx extent; a.C1 = conv Cout (K), a.Cout = conv Cin, a.M = N * (OH/2) * (OW/2)
+int viai_conv_dgrad_s2_patch_launch(ConvArgs& a, hipStream_t st) {
+    if (a.amax == nullptr || a.g.IH % 8 != 0 || a.g.IW % 16 != 0 || a.g.OH != 2 * a.g.IH || a.g.OW != 2 * a.g.IW || a.C1 % 32 != 0) return (int)hipErrorInvalidValue;
+    a.nblk_m = (a.M + 127) / 128;
+    a.nblk_n = (a.Cout + 63) / 64;
+    constexpr int lds_p = 2 * 2 * 9 * 1536;
+    static bool attr_p = false;
+    if (!attr_p) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dgrad_s2_patch_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_p);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dgrad_s2_patch_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_p);
+        attr_p = true;
+    }
+    if (a.in_p16) VIAI_LAUNCH(conv_dgrad_s2_patch_kernel<true>, dim3(a.nblk_m * a.nblk_n), dim3(256), lds_p, st, a);
+    else VIAI_LAUNCH(conv_dgrad_s2_patch_kernel<false>, dim3(a.nblk_m * a.nblk_n), dim3(256), lds_p, st, a);
+    return viai_launch_status();
+}
+
 int viai_conv_dgrad_s2_bf3_launch(ConvArgs& a, hipStream_t st) {
-    // a.g: N, IH/IW = dy extent, OH/OW = dx extent; a.C1 = conv Cout (K), a.Cout = conv Cin, a.M = N * (OH/2) * (OW/2)
     a.nblk_m = (a.M + 127) / 128;
     a.nblk_n = (a.Cout + 63) / 64;
     constexpr int lds = 2 * 3 * 128 * BF3_PITCH;
@@ -408,22 +430,7 @@ int viai_conv_dgrad_s2_bf3_launch(ConvArgs& a, hipStream_t st) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dgrad_s2_bf3_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_done = true;
     }
-    constexpr int patch = 1;
-    if (a.amax != nullptr && patch && a.g.IH % 8 == 0 && a.g.IW % 16 == 0 && a.g.OH == 2 * a.g.IH && a.g.OW == 2 * a.g.IW && a.C1 % 32 == 0) {
-        constexpr int lds_p = 2 * 2 * 9 * 1536;
-        static bool attr_p = false;
-        if (!attr_p) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dgrad_s2_patch_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_p);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dgrad_s2_patch_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_p);
-            attr_p = true;
-        }
-        viai_tag_kernel("dgrad_s2_patch_f16x2");
-        if (a.in_p16) VIAI_LAUNCH(conv_dgrad_s2_patch_kernel<true>, dim3(a.nblk_m * a.nblk_n), dim3(256), lds_p, st, a);
-        else VIAI_LAUNCH(conv_dgrad_s2_patch_kernel<false>, dim3(a.nblk_m * a.nblk_n), dim3(256), lds_p, st, a);
-        return viai_launch_status();
-    }
     if (a.in_p16 && (a.amax == nullptr || a.C1 % 32 != 0)) return (int)hipErrorInvalidValue;
-    viai_tag_kernel(a.amax != nullptr ? "dgrad_s2_f16x2" : "dgrad_s2_bf16x3");
     if (a.in_p16) VIAI_LAUNCH((conv_dgrad_s2_bf3_kernel<2, true>), dim3(a.nblk_m * a.nblk_n), dim3(256), 2 * 2 * 128 * BF3_PITCH, st, a);
     else if (a.amax != nullptr) VIAI_LAUNCH(conv_dgrad_s2_bf3_kernel<2>, dim3(a.nblk_m * a.nblk_n), dim3(256), 2 * 2 * 128 * BF3_PITCH, st, a);   // f16x2
     else VIAI_LAUNCH(conv_dgrad_s2_bf3_kernel<3>, dim3(a.nblk_m * a.nblk_n), dim3(256), lds, st, a);

@@ -10,7 +10,6 @@
 // Inpainting_Networks.py:60-110 (MelEncoder/MelDecoder) and their autograd data gradients.
 #include "viai_common.h"
 #include "viai_internal.h"
-#include <string>
 #include "viai_bf3.h"
 #include <type_traits>
 
@@ -695,7 +694,6 @@ int launch_halo(ConvArgs& a, int hy0, int hx0, hipStream_t st) {
     if (per_cu > 4) per_cu = 4;
     int grid = 256 * per_cu;
     if (grid > a.nblk_m) grid = a.nblk_m;
-    viai_tag_kernel(NP == 2 ? "halo_f16x2" : "halo_bf16x3");
     if constexpr (NP == 2) {
         if (a.in_p16) {
             static bool attr_p = false;
@@ -733,52 +731,41 @@ bool viai_conv_halo_ok(const ConvGeom& g, int C1, int C2, int Cout) {
 
 // f16x2 register-resident-filter variant: 32 input channels, <= 32 output channels, all nine positions of a 3 x 3 window
 bool viai_conv_halo16_ok(const ConvGeom& g, int C1, int C2, int Cout) {
-    constexpr int on = 1;
-    if (!on || !viai_conv_halo_ok(g, C1, C2, Cout) || C1 != 32 || Cout > 32 || g.ntaps != 9 || g.my != 1 || g.ly != 1) return false;
-    int y0 = g.dy[0], x0 = g.dx[0];
-    for (int t = 1; t < 9; ++t) { y0 = g.dy[t] < y0 ? g.dy[t] : y0; x0 = g.dx[t] < x0 ? g.dx[t] : x0; }
-    unsigned seen = 0;
-    for (int t = 0; t < 9; ++t) seen |= 1u << ((g.dy[t] - y0) * 3 + (g.dx[t] - x0));
-    return seen == 0x1ffu;
+    if (!viai_conv_halo_ok(g, C1, C2, Cout) || C1 != 32 || Cout > 32 || g.my != 1 || g.ly != 1) return false;
+    return viai_window9(g, nullptr, nullptr, nullptr);
 }
 
+// the streamed-filter kernel: bf16x3, or f16x2 fragment-major weights (64-channel / wide layers)
 int viai_conv_halo_bf3_launch(ConvArgs& a, hipStream_t st) {
     const ConvGeom& g = a.g;
     if (!viai_conv_halo_ok(g, a.C1, a.C2, a.Cout)) return (int)hipErrorInvalidValue;
     if (a.OC1 % 32 != 0 && a.OC1 != a.Cout) return (int)hipErrorInvalidValue;
-    if (a.wfrag == 3 && !viai_conv_halo16_ok(g, a.C1, a.C2, a.Cout)) {      // f16x2, filter streamed from L2 (64-channel / wide layers)
-        int y0 = g.dy[0], x0 = g.dx[0];
-        for (int t = 1; t < g.ntaps; ++t) { y0 = g.dy[t] < y0 ? g.dy[t] : y0; x0 = g.dx[t] < x0 ? g.dx[t] : x0; }
-        const bool wide = a.Cout > 32;
+    int y0 = g.dy[0], x0 = g.dx[0];
+    for (int t = 1; t < g.ntaps; ++t) { y0 = g.dy[t] < y0 ? g.dy[t] : y0; x0 = g.dx[t] < x0 ? g.dx[t] : x0; }
+    const bool wide = a.Cout > 32;
+    if (a.wfrag == WL_FRAG_F16) {
         if (g.my == 2) return wide ? launch_halo<32, 2, 2, 2>(a, y0, x0, st) : launch_halo<32, 1, 2, 2>(a, y0, x0, st);
         if (a.C1 == 32) return wide ? launch_halo<32, 2, 2>(a, y0, x0, st) : launch_halo<32, 1, 2>(a, y0, x0, st);
         return wide ? launch_halo<64, 2, 2>(a, y0, x0, st) : launch_halo<64, 1, 2>(a, y0, x0, st);
     }
-    if (a.wfrag == 3) {                                        // f16x2 fragment-major weights, filter in registers
-        int y0 = g.dy[0], x0 = g.dx[0];
-        for (int t = 1; t < 9; ++t) { y0 = g.dy[t] < y0 ? g.dy[t] : y0; x0 = g.dx[t] < x0 ? g.dx[t] : x0; }
-        HaloSlots sl;
-        for (int t = 0; t < 9; ++t) sl.s[(g.dy[t] - y0) * 3 + (g.dx[t] - x0)] = g.ws[t];
-        const size_t lds = (size_t)2 * HT_HP * 80;
-        a.nblk_m = a.M / 128;
-        a.nblk_n = 1;
-        int grid = 256 * 2;
-        if (grid > a.nblk_m) grid = a.nblk_m;
-        viai_tag_kernel("halo_c32_f16x2");
-        if (viai_conv_halo_c32_dma_ok(a)) return viai_conv_halo_c32_dma_launch(a, y0, x0, sl.s, st);      // round 5: patch by LDS-DMA, three tiles deep
-        if (a.in_p16) VIAI_LAUNCH(conv_halo_f16_c32_kernel<true>, dim3(grid), dim3(256), lds, st, a, y0, x0, a.nblk_m, sl);
-        else VIAI_LAUNCH(conv_halo_f16_c32_kernel<false>, dim3(grid), dim3(256), lds, st, a, y0, x0, a.nblk_m, sl);
-        return viai_launch_status();
-    }
-    int y0 = g.dy[0], y1 = g.dy[0], x0 = g.dx[0], x1 = g.dx[0];
-    for (int t = 1; t < g.ntaps; ++t) {
-        y0 = g.dy[t] < y0 ? g.dy[t] : y0; y1 = g.dy[t] > y1 ? g.dy[t] : y1;
-        x0 = g.dx[t] < x0 ? g.dx[t] : x0; x1 = g.dx[t] > x1 ? g.dx[t] : x1;
-    }
-    const bool wide = a.Cout > 32;
     if (g.my == 2) return wide ? launch_halo<32, 2, 3, 2>(a, y0, x0, st) : launch_halo<32, 1, 3, 2>(a, y0, x0, st);
     if (a.C1 == 32) return wide ? launch_halo<32, 2>(a, y0, x0, st) : launch_halo<32, 1>(a, y0, x0, st);
     return wide ? launch_halo<64, 2>(a, y0, x0, st) : launch_halo<64, 1>(a, y0, x0, st);
+}
+
+// f16x2 fragment-major weights, filter in registers (viai_conv_halo16_ok)
+int viai_conv_halo_c32_launch(ConvArgs& a, hipStream_t st) {
+    int y0, x0;
+    HaloSlots sl;
+    if (a.wfrag != WL_FRAG_F16 || !viai_conv_halo16_ok(a.g, a.C1, a.C2, a.Cout) || !viai_window9(a.g, &y0, &x0, sl.s)) return (int)hipErrorInvalidValue;
+    const size_t lds = (size_t)2 * HT_HP * 80;
+    a.nblk_m = a.M / 128;
+    a.nblk_n = 1;
+    int grid = 256 * 2;
+    if (grid > a.nblk_m) grid = a.nblk_m;
+    if (a.in_p16) VIAI_LAUNCH(conv_halo_f16_c32_kernel<true>, dim3(grid), dim3(256), lds, st, a, y0, x0, a.nblk_m, sl);
+    else VIAI_LAUNCH(conv_halo_f16_c32_kernel<false>, dim3(grid), dim3(256), lds, st, a, y0, x0, a.nblk_m, sl);
+    return viai_launch_status();
 }
 
 // Stride-1 3 x 3 layers for the kernel above: one source with Cin a multiple of 32, one destination with 32, 64 or a multiple of 128
@@ -790,8 +777,8 @@ int viai_halo_tiles_y(const ConvGeom& g) { return (g.OH + HT_H - 1) / HT_H; }
 // to fill the chip that way, else 8
 int viai_halo_s2_rows(const ConvGeom& g) {
     if (g.my != 2 || g.OH % 4 != 0) return 8;
-    // (round 5) the loader / consumer kernel (conv_halo_dma.hip) writes one partial block per 4 x 16 pixels whatever the map size; the block geometry is a
-    // property of the LAYER (viai_conv2d_stat_geom does not know which kernel will run), so the register-staged kernel follows on every map that kernel takes
+    // the loader / consumer kernel (conv_halo_dma.hip) writes one partial block per 4 x 16 pixels whatever the map size: the register-staged kernel follows
+    // on every map that kernel takes (one partial geometry per layer: route_fwd in conv_api.hip)
     if (viai_halo_dma_on() && g.OH % 8 == 0 && g.OW % 16 == 0 && g.IH == 2 * g.OH && g.IW == 2 * g.OW) return 4;
     return (long)g.N * (g.OH / 4) * viai_halo_tiles_x(g) >= 512 ? 4 : 8;
 }
@@ -809,24 +796,13 @@ bool viai_conv_halo_wide_ok(const ConvArgs& a) {
         // reference's native 80 x 208 clips): 68 %, 7 x 7: 38 % (stays on the gather kernel)
         if (g.my != 1 || (long)g.OH * g.OW * 3 < (long)viai_halo_tiles_y(g) * viai_halo_tiles_x(g) * HT_H * HT_W * 2) return false;
     }
-    if (g.my == 2) {                                               // stride-2 forward: eight-wave instances only, one source
-        constexpr int s2 = 1;
-        if (!s2 || a.C2 != 0 || a.Cout % 128 != 0 || a.OC1 != a.Cout) return false;
-    }
+    if (g.my == 2 && (a.C2 != 0 || a.Cout % 128 != 0 || a.OC1 != a.Cout)) return false;      // stride-2 forward: eight-wave instances only, one source
     const long tiles = (long)g.N * viai_halo_tiles_y(g) * viai_halo_tiles_x(g);
     // small maps: 64-channel blocks double the block count (the 16 x 32 maps of G.convblock2: 64 tiles -> 128 / 256 blocks, each
     // with half the K-loop work of a 128-channel block) -- still better than the split-K kernel those layers ran on
     constexpr long min64 = 96;
     if (tiles * (a.Cout >= 128 ? a.Cout / 128 : 1) < 192 && !(a.Cout >= 128 && tiles * (a.Cout / 64) >= min64)) return false;
-    int y0 = g.dy[0], x0 = g.dx[0];
-    for (int t = 1; t < 9; ++t) { y0 = g.dy[t] < y0 ? g.dy[t] : y0; x0 = g.dx[t] < x0 ? g.dx[t] : x0; }
-    unsigned seen = 0;
-    for (int t = 0; t < 9; ++t) {
-        const int r = g.dy[t] - y0, c = g.dx[t] - x0;
-        if (r > 2 || c > 2) return false;
-        seen |= 1u << (r * 3 + c);
-    }
-    return seen == 0x1ffu;
+    return viai_window9(g, nullptr, nullptr, nullptr);
 }
 
 template <int WM, int WN, int TM, int TN, int S = 1>
@@ -841,38 +817,44 @@ static int launch_halo_wide(ConvArgs& a, int y0, int x0, const HaloWideSlots& sl
         attr_done = true;
     }
     a.nblk_n = (a.Cout + 32 * TN * WN - 1) / (32 * TN * WN);
-    static const std::string fam = S == 2 ? std::string("halo_wide_s2_f16x2") : "halo_wide" + std::to_string(32 * TN * WN) + "_f16x2";
-    viai_tag_kernel(fam.c_str());
     if (a.in_p16 && (a.C2 != 0 || a.amax == nullptr)) return (int)hipErrorInvalidValue;          // one pre-split source, with its scale
     if (a.in_p16) VIAI_LAUNCH((conv_halo_wide_f16_kernel<WM, WN, TM, TN, S, true>), dim3(a.nblk_m * a.nblk_n), dim3(64 * WM * WN), lds, st, a, y0, x0, sl);
     else VIAI_LAUNCH((conv_halo_wide_f16_kernel<WM, WN, TM, TN, S, false>), dim3(a.nblk_m * a.nblk_n), dim3(64 * WM * WN), lds, st, a, y0, x0, sl);
     return viai_launch_status();
 }
 
-int viai_conv_halo_wide_launch(ConvArgs& a, hipStream_t st) {
+// register-staged instance: 0 / 1 = stride 2 with 4 / 8 tile rows, else by the channels of a block: 2 = 32, 3 = 64, 4 = 256, 5 = 128
+static int halo_wide_inst(const ConvArgs& a) {
     const ConvGeom& g = a.g;
-    if (!viai_conv_halo_wide_ok(a)) return (int)hipErrorInvalidValue;
-    int y0 = g.dy[0], x0 = g.dx[0];
-    for (int t = 1; t < 9; ++t) { y0 = g.dy[t] < y0 ? g.dy[t] : y0; x0 = g.dx[t] < x0 ? g.dx[t] : x0; }
-    HaloWideSlots sl;
-    for (int t = 0; t < 9; ++t) sl.s[(g.dy[t] - y0) * 3 + (g.dx[t] - x0)] = g.ws[t];
-    a.nblk_m = g.N * viai_halo_tiles_y(g) * viai_halo_tiles_x(g);
     // (stride 2 keeps the 64-pixel wave tiles: <1,8,4,1,2> 70.7 vs 72.1 us on D.conv2_2 but with spills, <1,4,4,1,2> 269 vs 101 us on D.conv2_1)
     // round 4: 64-pixel tiles (4 x 16) for the stride-2 forward where the map allows: half the LDS (49 KB), four waves per block, so TWO blocks
     // share a CU and one block's patch load / epilogue runs under the other's MFMAs -- the 128-pixel block is alone on its CU (98 KB, one LDS
     // stage) and its K loop is only 2 .. 4 chunks long, so nothing covered its prologue and epilogue
-    if (g.my == 2 && viai_conv_s2_dma_ok(a)) { viai_tag_kernel("halo_wide_s2_f16x2"); return viai_conv_s2_dma_launch(a, st); }
-    if (g.my == 1 && viai_conv_s1_dma_ok(a)) { viai_tag_kernel("halo_wide256_f16x2"); return viai_conv_s1_dma_launch(a, st); }
-    if (g.my == 2 && viai_halo_s2_rows(g) == 4) return (a.Cout % 256 == 0) ? launch_halo_wide<1, 4, 2, 2, 2>(a, y0, x0, sl, st) : launch_halo_wide<1, 4, 2, 1, 2>(a, y0, x0, sl, st);
-    if (g.my == 2) return (a.Cout % 256 == 0) ? launch_halo_wide<2, 4, 2, 2, 2>(a, y0, x0, sl, st) : launch_halo_wide<2, 4, 2, 1, 2>(a, y0, x0, sl, st);
-    if (a.Cout == 32) return launch_halo_wide<4, 1, 1, 1>(a, y0, x0, sl, st);
-    if (a.Cout == 64 || (long)a.nblk_m * (a.Cout / 128) < 192) return launch_halo_wide<2, 2, 2, 1>(a, y0, x0, sl, st);
-    constexpr int wn4 = 1;
+    if (g.my == 2) return viai_halo_s2_rows(g) == 4 ? 0 : 1;
+    const long tiles = (long)g.N * viai_halo_tiles_y(g) * viai_halo_tiles_x(g);
+    if (a.Cout == 32) return 2;
+    if (a.Cout == 64 || tiles * (a.Cout / 128) < 192) return 3;
     // 256-channel blocks: eight waves, each ALL 128 pixels x 32 channels (<1,8,4,1>) rather than 64 x 64 (<2,4,2,2>): a weight fragment
     // then feeds four M tiles, so the fragment stream through L1 halves (2 KB per 12 MFMAs) while the patch reads from LDS double (8 KB) --
     // LDS has twice L1's bandwidth, and the registers drop 231 -> 215.  D.conv3 203.5 -> 198 us, step 7.455 -> 7.423 ms (same box A/B).
-    constexpr int tm4 = 1;
-    if (tm4 && a.Cout % 256 == 0 && (long)a.nblk_m * (a.Cout / 256) >= 256) return launch_halo_wide<1, 8, 4, 1>(a, y0, x0, sl, st);
-    if (wn4 && a.Cout % 256 == 0 && (long)a.nblk_m * (a.Cout / 256) >= 256) return launch_halo_wide<2, 4, 2, 2>(a, y0, x0, sl, st);
-    return launch_halo_wide<1, 4, 4, 1>(a, y0, x0, sl, st);           // (128-channel blocks, same reasoning: 899 -> 855 us on 1024 x 28 x 28 x 128, 122.5 -> 117 us on 16 x 64 x 128 x 128)
+    return (a.Cout % 256 == 0 && tiles * (a.Cout / 256) >= 256) ? 4 : 5;
+}
+const char* viai_conv_halo_wide_family(const ConvArgs& a) {
+    static const char* const fam[6] = {"halo_wide_s2_f16x2", "halo_wide_s2_f16x2", "halo_wide32_f16x2", "halo_wide64_f16x2", "halo_wide256_f16x2", "halo_wide128_f16x2"};
+    return fam[halo_wide_inst(a)];
+}
+
+int viai_conv_halo_wide_launch(ConvArgs& a, hipStream_t st) {
+    int y0, x0;
+    HaloWideSlots sl;
+    if (!viai_conv_halo_wide_ok(a) || !viai_window9(a.g, &y0, &x0, sl.s)) return (int)hipErrorInvalidValue;
+    const bool c256 = a.Cout % 256 == 0;
+    switch (halo_wide_inst(a)) {
+    case 0: return c256 ? launch_halo_wide<1, 4, 2, 2, 2>(a, y0, x0, sl, st) : launch_halo_wide<1, 4, 2, 1, 2>(a, y0, x0, sl, st);
+    case 1: return c256 ? launch_halo_wide<2, 4, 2, 2, 2>(a, y0, x0, sl, st) : launch_halo_wide<2, 4, 2, 1, 2>(a, y0, x0, sl, st);
+    case 2: return launch_halo_wide<4, 1, 1, 1>(a, y0, x0, sl, st);
+    case 3: return launch_halo_wide<2, 2, 2, 1>(a, y0, x0, sl, st);
+    case 4: return launch_halo_wide<1, 8, 4, 1>(a, y0, x0, sl, st);
+    default: return launch_halo_wide<1, 4, 4, 1>(a, y0, x0, sl, st);          // (128-channel blocks, same reasoning: 899 -> 855 us on 1024 x 28 x 28 x 128, 122.5 -> 117 us on 16 x 64 x 128 x 128)
+    }
 }

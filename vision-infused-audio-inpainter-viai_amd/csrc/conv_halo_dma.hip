@@ -295,26 +295,26 @@ static unsigned long long* viai_dma_prof_buf = nullptr;
 #endif
 static unsigned tile_magic(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
 
-// P16 input, 32 -> 32 channels into one destination, byte offsets and tile counts within the 32-bit arithmetic of the kernel
+// 32 -> 32 channels into one destination, byte offsets and tile counts within the 32-bit arithmetic of the kernel (the launch: a P16 input with its scale)
 bool viai_conv_halo_c32_dma_ok(const ConvArgs& a) {
-    if (!viai_halo_dma_on() || !a.in_p16 || a.amax == nullptr || a.C1 != 32 || a.C2 != 0 || a.Cout != 32 || a.OC1 != 32) return false;
+    if (!viai_halo_dma_on() || a.C1 != 32 || a.C2 != 0 || a.Cout != 32 || a.OC1 != 32) return false;
     const ConvGeom& g = a.g;
     if ((long)g.N * g.IH * g.IW * 128 >= (1l << 31) || (long)g.N * g.OH * g.OW * 128 >= (1l << 31)) return false;
     const long tiles = (long)g.N * (g.OH / DT_H) * (g.OW / DT_W);
     return g.OH % DT_H == 0 && g.OW % DT_W == 0 && tiles * 64 < (1l << 31);
 }
 
-// P16 launches of the register-filter halo kernel's layers (viai_conv_halo16_ok): called by viai_conv_halo_bf3_launch
-int viai_conv_halo_c32_dma_launch(ConvArgs& a, int y0, int x0, const int* slots9, hipStream_t st) {
-    if (!viai_conv_halo_c32_dma_ok(a)) return (int)hipErrorInvalidValue;
+// P16 launches of the register-filter halo kernel's layers (viai_conv_halo16_ok)
+int viai_conv_halo_c32_dma_launch(ConvArgs& a, hipStream_t st) {
+    int y0, x0;
+    DmaSlots sl;
+    if (!a.in_p16 || a.amax == nullptr || !viai_conv_halo_c32_dma_ok(a) || !viai_window9(a.g, &y0, &x0, sl.s)) return (int)hipErrorInvalidValue;
     constexpr int lds = DP_NSTG * DP_STAGE + 4 * 2 * 32 * (int)sizeof(float);
     static bool attr_done = false;
     if (!attr_done) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo_c32_dma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_done = true;
     }
-    DmaSlots sl;
-    for (int t = 0; t < 9; ++t) sl.s[t] = slots9[t];
     a.nblk_m = a.M / 128;
     a.nblk_n = 1;
     int grid = 256 * 2;
@@ -1225,18 +1225,17 @@ __global__ __launch_bounds__(S2_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 
 }  // namespace
 
-// stride-2 3 x 3 pad-1 forward layers the producer / consumer kernel takes: P16 input with Cin a multiple of 32 (one source), Cout a multiple
-// of 128 into one destination, the input exactly twice the output, whole 8 x 16 tiles, 32-bit byte offsets
+// the full 3 x 3 window around the output pixel (padding 1): slot table by window position
+static bool pad1_window(const ConvGeom& g, int* slots9) {
+    int y0, x0;
+    return viai_window9(g, &y0, &x0, slots9) && y0 == -1 && x0 == -1;
+}
+// 3 x 3 pad-1 layers the producer / consumer kernel takes (shape only: the launch also needs the P16 input and its scale): Cin a multiple of 32
+// (one source), Cout a multiple of 128 into one destination, whole 8 x 16 tiles, 32-bit byte offsets; stride 2 with the input exactly twice the output
 static bool wide_dma_common(const ConvArgs& a) {
     const ConvGeom& g = a.g;
-    if (!viai_halo_dma_on() || !a.in_p16 || a.amax == nullptr || a.C2 != 0 || a.C1 % 32 != 0 || a.Cout % 128 != 0 || a.OC1 != a.Cout) return false;
-    if (g.ntaps != 9 || g.OH % S2_TH != 0 || g.OW % S2_TW != 0 || g.ly != 1 || g.lx != 1 || g.SH != g.OH || g.SW != g.OW) return false;
-    unsigned seen = 0;
-    for (int t = 0; t < 9; ++t) {
-        if (g.dy[t] < -1 || g.dy[t] > 1 || g.dx[t] < -1 || g.dx[t] > 1) return false;
-        seen |= 1u << ((g.dy[t] + 1) * 3 + (g.dx[t] + 1));
-    }
-    if (seen != 0x1ffu) return false;
+    if (!viai_halo_dma_on() || a.C2 != 0 || a.C1 % 32 != 0 || a.Cout % 128 != 0 || a.OC1 != a.Cout) return false;
+    if (g.OH % S2_TH != 0 || g.OW % S2_TW != 0 || g.ly != 1 || g.lx != 1 || g.SH != g.OH || g.SW != g.OW || !pad1_window(g, nullptr)) return false;
     if ((long)g.N * g.IH * g.IW * a.C1 * 4 >= (1l << 31) || (long)g.N * g.OH * g.OW * a.Cout * 4 >= (1l << 31)) return false;
     const long items = (long)g.N * (g.OH / S2_TH) * (g.OW / S2_TW) * (a.Cout / 128);
     return items * 64 < (1l << 31);
@@ -1266,7 +1265,7 @@ static int launch_wide_dma(ConvArgs& a, hipStream_t st) {
     sa.tiles_x = g.OW / S2_TW; sa.tiles_y = g.OH / S2_TH; sa.mx = tile_magic(sa.tiles_x); sa.my = tile_magic(sa.tiles_y);
     sa.nnb = a.Cout / W::CW; sa.mnb = tile_magic(sa.nnb);
     sa.nitems = g.N * sa.tiles_y * sa.tiles_x * sa.nnb;
-    for (int t = 0; t < 9; ++t) sa.slot[(g.dy[t] + 1) * 3 + (g.dx[t] + 1)] = g.ws[t];
+    pad1_window(g, sa.slot);
 #ifdef VIAI_PROF
     sa.prof = viai_dma_prof_buf;
 #endif
@@ -1279,11 +1278,11 @@ static int launch_wide_dma(ConvArgs& a, hipStream_t st) {
 }
 
 int viai_conv_s2_dma_launch(ConvArgs& a, hipStream_t st) {
-    if (!viai_conv_s2_dma_ok(a)) return (int)hipErrorInvalidValue;
+    if (!a.in_p16 || a.amax == nullptr || !viai_conv_s2_dma_ok(a)) return (int)hipErrorInvalidValue;
     return launch_wide_dma<2, 1>(a, st);
 }
 int viai_conv_s1_dma_launch(ConvArgs& a, hipStream_t st) {
-    if (!viai_conv_s1_dma_ok(a)) return (int)hipErrorInvalidValue;
+    if (!a.in_p16 || a.amax == nullptr || !viai_conv_s1_dma_ok(a)) return (int)hipErrorInvalidValue;
     return launch_wide_dma<1, 2>(a, st);
 }
 
@@ -1294,20 +1293,13 @@ static int lin_dma_pw(int Cout) { return Cout % 256 == 0 ? 1 : Cout % 128 == 0 ?
 bool viai_conv_lin_dma_geom_ok(const ConvArgs& a) {
     const ConvGeom& g = a.g;
     if (!viai_halo_dma_on() || a.C2 != 0 || a.C1 % 32 != 0 || a.Cout % 64 != 0 || a.OC1 != a.Cout) return false;
-    if (g.ntaps != 9 || g.ly != 1 || g.lx != 1 || g.my != 1 || g.mx != 1 || g.SH != g.OH || g.SW != g.OW || g.IH != g.OH || g.IW != g.OW || g.OW > 63) return false;
-    unsigned seen = 0;
-    for (int t = 0; t < 9; ++t) {
-        if (g.dy[t] < -1 || g.dy[t] > 1 || g.dx[t] < -1 || g.dx[t] > 1) return false;
-        seen |= 1u << ((g.dy[t] + 1) * 3 + (g.dx[t] + 1));
-    }
-    if (seen != 0x1ffu) return false;
+    if (g.ly != 1 || g.lx != 1 || g.my != 1 || g.mx != 1 || g.SH != g.OH || g.SW != g.OW || g.IH != g.OH || g.IW != g.OW || g.OW > 63 || !pad1_window(g, nullptr)) return false;
     const long M = (long)g.N * g.OH * g.OW;
     const int pw = lin_dma_pw(a.Cout);
     if (M % (128 * pw) != 0 || M * a.C1 * 4 >= (1l << 31) || M * a.Cout * 4 >= (1l << 31)) return false;
     if (g.OH % S2_TH == 0 && g.OW % S2_TW == 0 && a.Cout % 256 == 0) return false;
     return (M / (128 * pw)) * (a.Cout / (256 / pw)) >= 256;
 }
-bool viai_conv_lin_dma_ok(const ConvArgs& a) { return a.in_p16 && a.amax != nullptr && viai_conv_lin_dma_geom_ok(a); }
 
 // BatchNorm partials of the linear-tile kernel merged per persistent block and consumer wave: layers with ONE channel block (Cout = 64 / 128 / 256), where a
 // wave's channels are the same for every item.  parts = blocks x PW; part p = (block p / PW, pixel sub-block p % PW) covers 128 x (items of that block) pixels
@@ -1341,7 +1333,7 @@ static int launch_lin_dma(ConvArgs& a, hipStream_t st) {
     sa.rhw = 1.0f / (float)sa.HW; sa.mw = tile_magic(sa.W);
     sa.nnb = a.Cout / L::CW; sa.mnb = tile_magic(sa.nnb);
     sa.nitems = sa.M / L::PIX * sa.nnb;
-    for (int t = 0; t < 9; ++t) sa.slot[(g.dy[t] + 1) * 3 + (g.dx[t] + 1)] = g.ws[t];
+    pad1_window(g, sa.slot);
 #ifdef VIAI_PROF
     sa.prof = viai_dma_prof_buf;
 #endif
@@ -1354,7 +1346,7 @@ static int launch_lin_dma(ConvArgs& a, hipStream_t st) {
     return viai_launch_status();
 }
 int viai_conv_lin_dma_launch(ConvArgs& a, hipStream_t st) {
-    if (!viai_conv_lin_dma_ok(a)) return (int)hipErrorInvalidValue;
+    if (!a.in_p16 || a.amax == nullptr || !viai_conv_lin_dma_geom_ok(a)) return (int)hipErrorInvalidValue;
     const int pw = lin_dma_pw(a.Cout);
     return pw == 1 ? launch_lin_dma<1>(a, st) : pw == 2 ? launch_lin_dma<2>(a, st) : launch_lin_dma<4>(a, st);
 }

@@ -26,7 +26,6 @@
 // (mean, M2) pairs that bn_finalize merges with Chan's formula in fp64.
 #include "viai_common.h"
 #include "viai_internal.h"
-#include <string>
 #include <cstdlib>
 
 namespace {
@@ -317,8 +316,6 @@ int launch_igemm(ConvArgs& a, hipStream_t st) {
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_done = true;
     }
-    static const std::string fam = "igemm" + std::to_string(BM) + "x" + std::to_string(BN) + "_f32";
-    viai_tag_kernel(fam.c_str());
     VIAI_LAUNCH((conv_igemm_kernel<BK, TM, TN, WM, WN>), dim3(a.nblk_m * a.nblk_n), dim3(256), lds, st, a);
     return viai_launch_status();
 }
@@ -343,24 +340,32 @@ __global__ void pack_weight_kernel(const float* __restrict__ w, float* __restric
 // have only 16..256 such tiles, so they take 64x64 tiles (4x the blocks, 1/4 the per-block latency).
 int viai_igemm_tile_m(long M, int n_out) {
     if (n_out <= 32) return 128;
-    constexpr int force = 0;
-    if (force == 64 || force == 128) return force;
     long b128 = ((M + 127) / 128) * ((n_out + 127) / 128);
     if (n_out > 64) return b128 >= 512 ? 128 : 64;
     long b64 = ((M + 127) / 128) * ((n_out + 63) / 64);
     return b64 >= 512 ? 128 : 64;
 }
 
+bool viai_conv_igemm_ok(int C1, int C2, int Cout, int OC1) {
+    if ((C1 + C2) % 4 != 0 || (C2 > 0 && C1 % 32 != 0)) return false;
+    if (OC1 % 32 != 0 && OC1 != Cout) return false;
+    return !(Cout % 4 != 0 && Cout < 4);
+}
+// tile instance: 0 = 64 x 64, else 128 rows x 128 / 64 / 32 channels
+static int igemm_inst(long M, int n_out) { return viai_igemm_tile_m(M, n_out) == 64 ? 0 : n_out > 64 ? 1 : n_out > 32 ? 2 : 3; }
+const char* viai_conv_igemm_family(long M, int n_out) {
+    static const char* const fam[4] = {"igemm64x64_f32", "igemm128x128_f32", "igemm128x64_f32", "igemm128x32_f32"};
+    return fam[igemm_inst(M, n_out)];
+}
+
 int viai_conv_igemm_launch(ConvArgs& a, hipStream_t st) {
-    const int Cin = a.C1 + a.C2;
-    if (Cin % 4 != 0 || (a.C2 > 0 && a.C1 % 32 != 0)) return (int)hipErrorInvalidValue;
-    if (a.OC1 % 32 != 0 && a.OC1 != a.Cout) return (int)hipErrorInvalidValue;
-    if (a.Cout % 4 != 0 && a.Cout < 4) return (int)hipErrorInvalidValue;
-    const int bm = viai_igemm_tile_m(a.M, a.Cout);
-    if (bm == 64) return launch_igemm<32, 1, 1, 2, 2>(a, st);
-    if (a.Cout > 64) return launch_igemm<32, 2, 2, 2, 2>(a, st);
-    if (a.Cout > 32) return launch_igemm<32, 2, 1, 2, 2>(a, st);
-    return launch_igemm<32, 1, 1, 4, 1>(a, st);
+    if (!viai_conv_igemm_ok(a.C1, a.C2, a.Cout, a.OC1)) return (int)hipErrorInvalidValue;
+    switch (igemm_inst(a.M, a.Cout)) {
+    case 0: return launch_igemm<32, 1, 1, 2, 2>(a, st);
+    case 1: return launch_igemm<32, 2, 2, 2, 2>(a, st);
+    case 2: return launch_igemm<32, 2, 1, 2, 2>(a, st);
+    default: return launch_igemm<32, 1, 1, 4, 1>(a, st);
+    }
 }
 
 extern "C" int viai_pack_weight(const float* w, float* wp, int n_out, int k_in, int taps,

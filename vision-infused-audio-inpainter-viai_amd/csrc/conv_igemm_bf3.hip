@@ -14,7 +14,6 @@
 // planes [plane][row][32 + 8 pad] (80-byte rows: conflict-free ds_read_b128 operand fetches).
 #include "viai_common.h"
 #include "viai_internal.h"
-#include <string>
 #include "viai_bf3.h"
 // timing ablation of the wide kernel: bit 0 no weight-fragment loads, bit 1 no activation loads, bit 2 no split / LDS stores
 #ifndef VIAI_ABL
@@ -921,8 +920,6 @@ static int launch_bf3(ConvArgs& a, hipStream_t st) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_done = true;
     }
-    static const std::string fam = "igemm" + std::to_string(BM) + "x" + std::to_string(BN) + (NP == 2 ? "_f16x2" : "_bf16x3");
-    viai_tag_kernel(fam.c_str());
     VIAI_LAUNCH(kern, dim3(a.nblk_m * a.nblk_n), dim3(64 * WM * WN), lds, st, a);
     return viai_launch_status();
 }
@@ -934,51 +931,56 @@ bool viai_bf3_frag_layout(long M, int n_out) { return viai_igemm_tile_m(M, n_out
 // The split-K kernel takes the layers whose 64 x 64 tiling would leave most CUs idle.
 bool viai_bf3_sk_ok(long M, int n_out, int C1, int C2) {
     if ((C1 + C2) % 16 != 0 || (C2 > 0 && C1 % 64 != 0)) return false;
-    constexpr int mode = 1;
-    if (!mode) return false;
     long b64 = ((M + 63) / 64) * ((n_out + 63) / 64);
     return n_out > 32 && b64 < 512;
 }
 
-static int launch_bf3_sk(ConvArgs& a, hipStream_t st) {
+static bool bf3_args_ok(const ConvArgs& a) {
+    const int Cin = a.C1 + a.C2;
+    if (Cin % 16 != 0 || (a.C2 > 0 && a.C1 % 32 != 0)) return false;
+    if (a.OC1 % 32 != 0 && a.OC1 != a.Cout) return false;
+    return !a.in_p16;                                       // only the patch-staged kernels stage P16 pieces
+}
+
+int viai_conv_igemm_sk_launch(ConvArgs& a, hipStream_t st) {
+    if (!bf3_args_ok(a) || wl_frag(a.wfrag)) return (int)hipErrorInvalidValue;
     a.nblk_m = (a.M + 31) / 32;
     a.nblk_n = (a.Cout + 31) / 32;
     constexpr int lds = 2 * 3 * 32 * (64 * 2 + 16);
-    viai_tag_kernel(a.wfrag == 4 ? "igemm_sk32x32_f16x2" : "igemm_sk32x32_bf16x3");
-    if (a.wfrag == 4) VIAI_LAUNCH(conv_igemm_bf3_sk_kernel<2>, dim3(a.nblk_m * a.nblk_n), dim3(256), lds, st, a);       // planar f16x2 weights
+    if (a.wfrag == WL_PLANAR_F16) VIAI_LAUNCH(conv_igemm_bf3_sk_kernel<2>, dim3(a.nblk_m * a.nblk_n), dim3(256), lds, st, a);
     else VIAI_LAUNCH(conv_igemm_bf3_sk_kernel<3>, dim3(a.nblk_m * a.nblk_n), dim3(256), lds, st, a);
     return viai_launch_status();
 }
 
+// tile instance: the planar layouts follow the tile rule of the fp32 kernels (BN partial geometry): 0 = 64 x 64, 1 .. 3 = 128 rows x 128 / 64 / 32
+// channels; the fragment-major layouts run 128 x 128 (1) or, f16x2 only, 4 = 128 x 256 (eight waves) where the layer is wide and tall enough: every
+// staged activation row then feeds 256 output channels, halving the load / split / LDS-store work per MFMA
+static int bf3_inst(int layout, long M, int n_out) {
+    if (layout == WL_FRAG_F16 && n_out % 256 == 0 && ((M + 127) / 128) * (n_out / 256) >= 256) return 4;
+    if (wl_frag(layout)) return 1;
+    return viai_igemm_tile_m(M, n_out) == 64 ? 0 : n_out > 64 ? 1 : n_out > 32 ? 2 : 3;
+}
+const char* viai_conv_igemm_bf3_family(int layout, long M, int n_out) {
+    static const char* const fam[2][5] = {
+        {"igemm64x64_bf16x3", "igemm128x128_bf16x3", "igemm128x64_bf16x3", "igemm128x32_bf16x3", nullptr},
+        {"igemm64x64_f16x2", "igemm128x128_f16x2", "igemm128x64_f16x2", "igemm128x32_f16x2", "igemm128x256_f16x2"}};
+    return fam[wl_f16(layout) ? 1 : 0][bf3_inst(layout, M, n_out)];
+}
+
 int viai_conv_igemm_bf3_launch(ConvArgs& a, hipStream_t st) {
-    const int Cin = a.C1 + a.C2;
-    if (Cin % 16 != 0 || (a.C2 > 0 && a.C1 % 32 != 0)) return (int)hipErrorInvalidValue;
-    if (a.OC1 % 32 != 0 && a.OC1 != a.Cout) return (int)hipErrorInvalidValue;
-    if (a.in_p16 && !(a.wfrag == 3 && !a.sk && (viai_conv_halo_wide_ok(a) || viai_conv_lin_dma_ok(a)))) return (int)hipErrorInvalidValue;     // only the patch-staged kernels stage P16 pieces
-    if (a.sk) return launch_bf3_sk(a, st);
-    const int bm = viai_igemm_tile_m(a.M, a.Cout);           // same tile rule as the fp32 kernels (BN partial geometry)
-    if (a.wfrag == 3) {                                                        // f16x2 weights
-        if (viai_conv_lin_dma_ok(a)) { viai_tag_kernel("lin_dma_f16x2"); return viai_conv_lin_dma_launch(a, st); }   // pre-split input, maps that are not whole 8 x 16 tiles
-        if (viai_conv_halo_wide_ok(a)) return viai_conv_halo_wide_launch(a, st);   // stride-1 3 x 3: patch staged once per chunk, not once per tap
-        // 128 x 256 tile (eight waves) where the layer is wide and tall enough: every staged activation row then feeds 256
-        // output channels, halving the load / split / LDS-store work per MFMA
-        constexpr int wn4 = 1;
-        if (wn4 && a.Cout % 256 == 0 && ((a.M + 127) / 128) * (a.Cout / 256) >= 256) {
-            return launch_bf3<true, 2, 2, 2, 4, 2>(a, st);
-        }
-        return launch_bf3<true, 2, 2, 2, 2, 2>(a, st);
+    if (!bf3_args_ok(a)) return (int)hipErrorInvalidValue;
+    const int inst = bf3_inst(a.wfrag, a.M, a.Cout);
+    switch (a.wfrag) {
+    case WL_FRAG_F16: return inst == 4 ? launch_bf3<true, 2, 2, 2, 4, 2>(a, st) : launch_bf3<true, 2, 2, 2, 2, 2>(a, st);
+    case WL_FRAG_BF3: return launch_bf3<true, 2, 2, 2, 2>(a, st);
+    case WL_PLANAR_F16:
+        return inst == 0 ? launch_bf3<false, 1, 1, 2, 2, 2>(a, st) : inst == 1 ? launch_bf3<false, 2, 2, 2, 2, 2>(a, st)
+             : inst == 2 ? launch_bf3<false, 2, 1, 2, 2, 2>(a, st) : launch_bf3<false, 1, 1, 4, 1, 2>(a, st);
+    case WL_PLANAR_BF3:
+        return inst == 0 ? launch_bf3<false, 1, 1, 2, 2>(a, st) : inst == 1 ? launch_bf3<false, 2, 2, 2, 2>(a, st)
+             : inst == 2 ? launch_bf3<false, 2, 1, 2, 2>(a, st) : launch_bf3<false, 1, 1, 4, 1>(a, st);
+    default: return (int)hipErrorInvalidValue;
     }
-    if (a.wfrag && a.wfrag != 4) return launch_bf3<true, 2, 2, 2, 2>(a, st);
-    if (a.wfrag == 4) {                                                        // planar f16x2 weights
-        if (bm == 64) return launch_bf3<false, 1, 1, 2, 2, 2>(a, st);
-        if (a.Cout > 64) return launch_bf3<false, 2, 2, 2, 2, 2>(a, st);
-        if (a.Cout > 32) return launch_bf3<false, 2, 1, 2, 2, 2>(a, st);
-        return launch_bf3<false, 1, 1, 4, 1, 2>(a, st);
-    }
-    if (bm == 64) return launch_bf3<false, 1, 1, 2, 2>(a, st);
-    if (a.Cout > 64) return launch_bf3<false, 2, 2, 2, 2>(a, st);
-    if (a.Cout > 32) return launch_bf3<false, 2, 1, 2, 2>(a, st);
-    return launch_bf3<false, 1, 1, 4, 1>(a, st);
 }
 
 size_t viai_bf3_packed_floats(int n_out, int k_in, int taps) {

@@ -418,7 +418,6 @@ int viai_conv_stem_fwd_launch(ConvArgs& a, hipStream_t st) {
     a.nblk_m = ntiles; a.nblk_n = 1;
     int grid = 512;
     if (grid > ntiles) grid = ntiles;
-    viai_tag_kernel("stem_f16x2");
     VIAI_LAUNCH(stem_fwd_f16_kernel, dim3(grid), dim3(256), lds, st, a, ntiles);
     return viai_launch_status();
 }
@@ -440,7 +439,6 @@ int viai_conv_stem_wgrad_launch(WgradArgs& a, int Cin, float* dw, int accumulate
     constexpr int lds = 2 * (2 * 64 * 128 + 2 * 13 * ST_PITCH);
     static bool attr_done = false;
     if (!attr_done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem_wgrad_f16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr_done = true; }
-    viai_tag_kernel("wgrad_stem_f16x2");
     VIAI_LAUNCH(stem_wgrad_f16_kernel, dim3(blocks), dim3(256), lds, st, a, ntiles, per);
     VIAI_LAUNCH(stem_wgrad_reduce_kernel, dim3(ST_K * ST_COUT), dim3(256), 0, st, (const float*)a.ws, dw, blocks, Cin, accumulate);
     return viai_launch_status();

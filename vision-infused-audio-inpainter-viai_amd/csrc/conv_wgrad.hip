@@ -335,7 +335,6 @@ int launch_wgrad(WgradArgs& a, hipStream_t st) {
         attr_done = true;
     }
     dim3 grid(a.nblk_co * a.nblk_ci * a.g.ntaps * a.ksplit);
-    viai_tag_kernel("wgrad_mfma_f32");
     VIAI_LAUNCH((wgrad_mfma_kernel<TM, TN, WM, WN>), grid, dim3(256), lds, st, a);
     return viai_launch_status();
 }
@@ -344,8 +343,7 @@ int launch_wgrad(WgradArgs& a, hipStream_t st) {
 
 // layers the all-taps 32-channel kernel takes
 bool viai_wgrad32_ok(const ConvGeom& g, int Cout, int C1, int C2) {
-    constexpr int on = 1;
-    if (!on || C2 != 0 || Cout > 32 || C1 > 32 || Cout % 4 != 0 || C1 % 4 != 0 || g.run) return false;
+    if (C2 != 0 || Cout > 32 || C1 > 32 || Cout % 4 != 0 || C1 % 4 != 0 || g.run) return false;
     if (g.mx != 1 || g.my != 1 || g.ly != 1 || g.lx != 1 || g.SH != g.OH || g.SW != g.OW || g.OW % 32 != 0 || g.ntaps < 1 || g.ntaps > 9) return false;
     int y0 = g.dy[0], y1 = g.dy[0], x0 = g.dx[0], x1 = g.dx[0];
     for (int t = 1; t < g.ntaps; ++t) {
@@ -385,7 +383,6 @@ int viai_wgrad32_launch(WgradArgs& a, int ksplit, hipStream_t st) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad32_halo_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_done = true;
     }
-    viai_tag_kernel("wgrad32_all_taps_f32");
     if (g.ntaps == 9) VIAI_LAUNCH(wgrad32_halo_kernel<true>, dim3(ksplit), dim3(256), lds, st, a, tp);
     else VIAI_LAUNCH(wgrad32_halo_kernel<false>, dim3(ksplit), dim3(256), lds, st, a, tp);
     return viai_launch_status();
@@ -409,17 +406,18 @@ int viai_wgrad_pick_ksplit(int Cout, int Cin, int ntaps, long M) {
     return (int)ks;
 }
 
+// channel counts in fours; with two sources, a 32-channel Cin tile must not straddle them
+bool viai_wgrad_mfma_ok(int Cout, int C1, int C2) { return (C1 + C2) % 4 == 0 && Cout % 4 == 0 && (C2 == 0 || C1 % 32 == 0); }
+
 int viai_wgrad_mfma_launch(WgradArgs& a, int ksplit, hipStream_t st) {
     const int Cin = a.C1 + a.C2;
-    if (Cin % 4 != 0 || a.Cout % 4 != 0) return (int)hipErrorInvalidValue;
+    if (!viai_wgrad_mfma_ok(a.Cout, a.C1, a.C2)) return (int)hipErrorInvalidValue;
     long chunks = ((long)a.M + BKP - 1) / BKP;
     a.ksplit = ksplit;
     a.chunks_per_split = (int)((chunks + ksplit - 1) / ksplit);
     int bm = tile_of(a.Cout), bn = tile_of(Cin);
-    if (a.C2 > 0) {                       // a Cin tile must not straddle the two concatenated sources
+    if (a.C2 > 0)                         // a Cin tile must not straddle the two concatenated sources
         while (bn > 32 && (a.C1 % bn) != 0) bn >>= 1;
-        if ((a.C1 % bn) != 0) return (int)hipErrorInvalidValue;
-    }
     if (bm == 128 && bn == 128) return launch_wgrad<2, 2, 2, 2>(a, st);
     if (bm == 128 && bn == 64) return launch_wgrad<2, 1, 2, 2>(a, st);
     if (bm == 128 && bn == 32) return launch_wgrad<2, 1, 2, 1>(a, st);   // 128 x 32, WK = 2

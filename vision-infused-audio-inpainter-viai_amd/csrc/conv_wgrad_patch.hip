@@ -384,22 +384,6 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32) * WK) __attribute__((amd
     }
 }
 
-static bool window9(const ConvGeom& g, int* y0, int* x0, WgPatchSlots* sl) {
-    if (g.ntaps != 9) return false;
-    int yy = g.dy[0], xx = g.dx[0];
-    for (int t = 1; t < 9; ++t) { yy = g.dy[t] < yy ? g.dy[t] : yy; xx = g.dx[t] < xx ? g.dx[t] : xx; }
-    unsigned seen = 0;
-    for (int t = 0; t < 9; ++t) {
-        const int r = g.dy[t] - yy, c = g.dx[t] - xx;
-        if (r > 2 || c > 2) return false;
-        seen |= 1u << (r * 3 + c);
-        if (sl) sl->s[r * 3 + c] = g.ws[t];
-    }
-    if (y0) *y0 = yy;
-    if (x0) *x0 = xx;
-    return seen == 0x1ffu;
-}
-
 // which instance takes a layer: 0 none, 1 = <1,128,64,4,1>, 2 = <2,128,32,2,1>, 3 = <1,32,32,4,4>, 4 = <1,64,64,2,1> (round 3: the 64-channel stride-1
 // layers -- ResNet-18 layer1 on 56 x 56 maps, G.convblock3 -- ran on the narrow instance, whose four waves stage a 32-channel dy row and a
 // 32-channel x patch for ONE 32 x 32 tile; four tiles per block halve the staging per MFMA)
@@ -408,7 +392,7 @@ static int pick(const ConvGeom& g, int Cout, int C1, int C2) {
     if (wgrad_patch_tiles(g) < 64) return 0;
     // partial tiles multiply zeros: refuse maps that would waste more than ~2/3 of the MFMAs (7 x 7: two images per tile, 98 of 128 pixels; 4 x 4: not taken)
     if ((long)g.N * g.OH * g.OW * 3 < wgrad_patch_tiles(g) * WP_TH * WP_TW) return 0;
-    if (!window9(g, nullptr, nullptr, nullptr)) return 0;
+    if (!viai_window9(g, nullptr, nullptr, nullptr)) return 0;
     if (g.my == 2) return (Cout % 128 == 0 && C1 % 32 == 0 && C2 % 32 == 0 && C1 >= 32) ? 2 : 0;
     if (Cout % 128 == 0 && C1 % 64 == 0 && C2 % 64 == 0 && C1 >= 64) return 1;
     if (Cout % 64 == 0 && C1 % 64 == 0 && C2 % 64 == 0 && C1 >= 64) return 4;
@@ -417,14 +401,12 @@ static int pick(const ConvGeom& g, int Cout, int C1, int C2) {
 }
 static int bm_of(int cfg) { return cfg == 3 ? 32 : cfg == 4 ? 64 : 128; }
 static int bn_of(int cfg) { return (cfg == 1 || cfg == 4) ? 64 : 32; }
-static int wk_of(int cfg) { (void)cfg; return 1; }      // slabs per block (the k-splitting waves of the narrow instance reduce in the block)
 
 template <int S, int BM, int BN, int HR, int WK, bool PD, bool PX>
 static int launch_patch_p(WgradArgs& a, int y0, int x0, const WgPatchSlots& sl, hipStream_t st) {
     using C = WgCfg<S, BM, BN, HR, WK>;
     static bool attr_done = false;
     if (!attr_done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_patch_f16_kernel<S, BM, BN, HR, WK, PD, PX>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS); attr_done = true; }
-    viai_tag_kernel(S == 2 ? "wgrad_patch_s2_f16x2" : BM == 32 ? "wgrad_patch_narrow_f16x2" : BM == 64 ? "wgrad_patch64_f16x2" : "wgrad_patch_f16x2");
     VIAI_LAUNCH((wgrad_patch_f16_kernel<S, BM, BN, HR, WK, PD, PX>), dim3(a.nblk_co * a.nblk_ci * a.ksplit), dim3(C::NTHR), C::LDS, st, a, y0, x0, sl);
     return viai_launch_status();
 }
@@ -458,35 +440,36 @@ static int block_ksplit(const ConvGeom& g, int Cout, int Cin, int cfg) {
 
 // 3 x 3 layers with the full window, stride 1 or 2 (plain conv), output extent a multiple of the 8 x 16 tile, enough tiles to give every
 // block a K loop worth its prologue / epilogue, and channel counts one of the instances tiles (a Cin tile must not straddle the two
-// concatenated sources).  `shape_ok` is the pure shape predicate (workspace sizing); `ok` adds the switches.
+// concatenated sources).  Without `switches` this is the pure shape rule (workspace sizing).
 //
 // Same-box A/B of the full three-stream step (the weight gradients run beside the main backward chain, so a kernel that is faster alone
 // but takes a CU's whole LDS / register file can still lose): neither patch kernel 8.69 ms, stride-1 instance only 8.54, both with two
 // stride-2 blocks per CU 8.45, both with ONE stride-2 block per CU (256 blocks) 8.37; + the narrow instance 8.17; and with the grids
 // cut below one block per CU (192 / 192 / 128 blocks: CUs left to the main chain, fewer slabs to reduce) 8.00 -- the defaults
 // VIAI_WGRAD_PATCH_S2=0 switches the stride-2 instance off.
-bool viai_wgrad_patch_shape_ok(const ConvGeom& g, int Cout, int C1, int C2) { return pick(g, Cout, C1, C2) != 0; }
-
-bool viai_wgrad_patch_ok(const ConvGeom& g, int Cout, int C1, int C2) {
+int viai_wgrad_patch_cfg(const ConvGeom& g, int Cout, int C1, int C2, bool switches) {
     const int cfg = pick(g, Cout, C1, C2);
-    if (cfg == 2) { const char* e = getenv("VIAI_WGRAD_PATCH_S2"); if (e && !atoi(e)) return false; }         // read per call: tests/test_fullsize_gpu.py switches it (the round-1 kernel stays covered)
-    return cfg != 0;
+    if (cfg == 2 && switches) { const char* e = getenv("VIAI_WGRAD_PATCH_S2"); if (e && !atoi(e)) return 0; }         // read per call: tests/test_fullsize_gpu.py switches it (the round-1 kernel stays covered)
+    return cfg;
+}
+const char* viai_wgrad_patch_family(int cfg) {
+    return cfg == 2 ? "wgrad_patch_s2_f16x2" : cfg == 3 ? "wgrad_patch_narrow_f16x2" : cfg == 4 ? "wgrad_patch64_f16x2" : "wgrad_patch_f16x2";
 }
 
 // total number of K slabs the launch writes (block-level slabs x waves that split the k-steps)
 int viai_wgrad_patch_ksplit(const ConvGeom& g, int Cout, int C1, int C2) {
     const int cfg = pick(g, Cout, C1, C2);
     if (cfg == 0) return 1;
-    return block_ksplit(g, Cout, C1 + C2, cfg) * wk_of(cfg);
+    return block_ksplit(g, Cout, C1 + C2, cfg);      // (the k-splitting waves of the narrow instance reduce in the block: one slab per block)
 }
 
 int viai_wgrad_patch_launch(WgradArgs& a, hipStream_t st) {
     const ConvGeom& g = a.g;
     const int Cin = a.C1 + a.C2;
-    if (a.amax == nullptr || !viai_wgrad_patch_ok(g, a.Cout, a.C1, a.C2)) return (int)hipErrorInvalidValue;
-    const int cfg = pick(g, a.Cout, a.C1, a.C2);
+    const int cfg = viai_wgrad_patch_cfg(g, a.Cout, a.C1, a.C2, true);
+    if (a.amax == nullptr || cfg == 0) return (int)hipErrorInvalidValue;
     int y0, x0; WgPatchSlots sl;
-    window9(g, &y0, &x0, &sl);
+    viai_window9(g, &y0, &x0, sl.s);
     const long tiles = wgrad_patch_tiles(g);
     a.ksplit = block_ksplit(g, a.Cout, Cin, cfg);
     a.chunks_per_split = (int)((tiles + a.ksplit - 1) / a.ksplit);
