@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VIAI_ABI_VERSION 18
+#define VIAI_ABI_VERSION 19
 
 enum { VIAI_ACT_NONE = 0, VIAI_ACT_RELU = 1, VIAI_ACT_LRELU = 2, VIAI_ACT_SIGMOID = 3 };
 
@@ -341,8 +341,36 @@ typedef struct viai_wn_synth {
     int* step;                              /* device int, 0 before the first call: counts the calls (the step advances it itself) */
     float* z2;                              /* fused stages: second (B, G/2) buffer (z is double-buffered) */
     int fused;                              /* 1: run the fused-stage form (needs layers[].w_stage / b_stage, z2; S, out_ch, G/2 <= 256) */
+    /* ---- categorical network (ABI v19): WaveNet(scalar_input=False), one-hot mu-law input and a softmax over K = out_ch classes.  All
+     * zero = the mixture-of-logistics network above, so a caller that does not know these fields is unaffected.  The 24 layer stages are
+     * the same; the two ends of the time step differ (wavenet.py:116-119 first conv over K input channels, :350-356 softmax / draw):
+     *   w_first    [C][K]  first-conv weight, dense input form: x0[b] = w_first . row_b + b_first (a row of K floats per stream)
+     *   w_first_t  [K][C]  the same weight transposed, class input form: x0[b] = w_first_t[class_b] + b_first (one contiguous row)
+     * Input of time step t (the rule of wavenet.py:322-327): t < n_test: teacher-forced, class form from test_classes (B, n_test) when
+     * that is given, else dense form from test_inputs (B, n_test, K); otherwise the previous step's output, class form from classes
+     * when cat_quantize, else dense form from yhat_dbg; t == 0 without test inputs: init_rows (B, K) when given, else class init_class
+     * (wavenet.py:308-312: 127).
+     * Output of time step t: cat_softmax 1 / cat_quantize 1: a class per stream into classes (B, T) -- the inclusive prefix sum of the K
+     * probabilities in class order (fp64, wave scan + carry over the four waves: fixed order), divided by its last element; the class is
+     * the number of entries <= u2[b][t], at most K - 1, which is np.random.choice(K, p) from one random_sample() (wavenet.py:353-354) -- and
+     * its one-hot row into yhat_dbg if given (:355-356); 1 / 0: the probabilities into yhat_dbg (:351); 0 / 0: the logits.  0 / 1 is
+     * refused (the reference hands logits to np.random.choice, which raises).
+     * In this mode u1 is unused, u2 (B, T) holds one uniform in [0, 1) per stream and step, yhat_dbg is (B, T, K) and REQUIRED unless
+     * cat_quantize, and `out` is scratch of B (S + K) floats (the head's hidden layer, the logits).  K <= 256, K % 4 == 0, B in {1,2,4,8};
+     * chain forms only: viai_wn_pipe_ok is 0 for such a descriptor.                                                                  */
+    int categorical, cat_softmax, cat_quantize, init_class;
+    const float* w_first_t;
+    const int* test_classes;
+    const float* init_rows;
+    int* classes;
 } viai_wn_synth;
 int viai_wavenet_synth_step(const viai_wn_synth* s, void* stream);
+/* host-only (no device needed): 1 if s is a categorical descriptor the chain forms run (the shape conditions above; pointers are checked
+ * by the step itself) */
+int viai_wn_categorical_ok(const viai_wn_synth* s);
+/* mu-law classes -> waveform in [-1, 1]: y = 2 k / mu - 1, x = sign(y) ((1 + mu)^|y| - 1) / mu (the inverse of the mulaw_quantize the reference's
+ * data preparation applies, utils/librivox.py:66-68; decoded there by utils/model_util.py:63-64); classes, out: n elements */
+int viai_mulaw_decode(const int* classes, float* out, long n, int mu, void* stream);
 /* The same time steps t0 .. t0 + n_steps - 1 launched from a host loop with the time index passed BY VALUE (ABI v5): no kernel starts
  * with a load of `*step` in front of its address arithmetic (a full memory round trip at these grid sizes).  `step` is not touched.
  * wavenet.py:237-364 incremental_forward's loop body, n_steps at a time.                                                         */
@@ -354,7 +382,8 @@ int viai_wavenet_synth_run(const viai_wn_synth* s, int t0, int n_steps, void* st
  * stages as tokens of 8-byte {tag, value} granules, so up to B stages work at once where the chain form (viai_wavenet_synth_run) has one.
  * Same time steps, same folded weights (layers[].w_stage / b_stage), fp32, fixed summation order; replaces the per-step loop of
  * wavenet.py:322-357 for this configuration.
- *   viai_wn_pipe_ok            1 if `s` is that configuration with 1 .. 32 streams and the device has >= 256 compute units (all blocks must be resident)
+ *   viai_wn_pipe_ok            1 if `s` is that configuration (mixture-of-logistics output: 0 for a categorical descriptor) with 1 .. 32 streams and
+ *                              the device has >= 256 compute units (all blocks must be resident)
  *   viai_wn_pipe_image_floats  sizes of the five weight images the HOST packs (viai_amd.wavenet._pipe_images): 0 wreg [24][10][8][156][64],
  *                              1 wlds [24][10][130][260], 2 bias [24][10][136], 3 head_w [544][256], 4 head_b [544], 5 wcond [24][10][64][80]
  *   viai_wn_pipe_token_granules  8-byte granules of the token rings for B streams (dil: the 24 dilations)

@@ -571,6 +571,122 @@ def wavenet_onehot_goldens():
     print("wavenet_onehot -> %s (%.1f KB)" % (os.path.relpath(path, ROOT), os.path.getsize(path) / 1024))
 
 
+class WNConfigOneHotDeep:
+    """oracle/wavenet_oracle.py's WNConfigDeep (the reference's depth: 24 layers / 4 stacks, dilations 1 .. 32 four times; 32 channels wide) with
+    one-hot input and 256 classes.  tests/test_wavenet_onehot_synth_*.py restate it."""
+    out_channels, layers, stacks, residual_channels, gate_channels, skip_out_channels = 256, 24, 4, 32, 32, 32
+    kernel_size, cin_channels, upsample_scales, freq_axis_kernel_size, gin_channels, n_speakers = 3, 80, (4, 4), 3, -1, None
+    scalar_input = False
+
+
+def inv_cdf_draw(p, u):
+    """np.random.choice(K, p=p) from ONE random_sample() draw u: cumsum in float64, normalised by its last element, searchsorted side="right"."""
+    cdf = np.cumsum(np.asarray(p, dtype=np.float64))
+    cdf /= cdf[-1]
+    return int(min(np.searchsorted(cdf, u, side="right"), cdf.size - 1)), cdf
+
+
+def wavenet_onehot_synth_goldens():
+    """Sample-by-sample synthesis of the one-hot (softmax) WaveNet from the reference's own `incremental_forward` (wavenet.py:237-364) in all three
+    modes it defines (:350-356).  `np.random.choice` is replaced for the duration of a run by `inv_cdf_draw` fed from closed-form uniforms, after one
+    check against the unpatched function under a seeded RandomState.  Two networks, the small one and one at the reference's depth; the closed-form
+    weights are sharpened (last 1x1 gain x 12, first-conv gain x 4 or more) so that what is fed back matters: both conditions are asserted here and
+    again by tests/test_wavenet_onehot_synth_cpu.py from the file."""
+    import Config  # noqa: F401
+    from oracle import wavenet_oracle as W
+    from wavenet_vocoder import wavenet as RW
+    torch.set_num_threads(1)
+    out = OrderedDict()
+    real_choice = np.random.choice
+
+    def make(cfg, tag, first_gain, last_gain):
+        net = RW.WaveNet(out_channels=cfg.out_channels, layers=cfg.layers, stacks=cfg.stacks, residual_channels=cfg.residual_channels,
+                         gate_channels=cfg.gate_channels, skip_out_channels=cfg.skip_out_channels, kernel_size=cfg.kernel_size, dropout=0.0,
+                         cin_channels=cfg.cin_channels, gin_channels=-1, n_speakers=None, weight_normalization=True,
+                         upsample_conditional_features=True, upsample_scales=list(cfg.upsample_scales),
+                         freq_axis_kernel_size=cfg.freq_axis_kernel_size, scalar_input=False)
+        sd = W.wavenet_state(cfg, tag)
+        sd["first_conv.weight_g"] = sd["first_conv.weight_g"] * first_gain
+        sd["last_conv_layers.3.weight_g"] = sd["last_conv_layers.3.weight_g"] * last_gain
+        assert list(net.state_dict().keys()) == list(sd.keys())
+        load_into(net, sd)
+        return net.eval()
+
+    def run(net, c, T, test_inputs, softmax, quantize, uniforms=None, choice=None):
+        """the reference's incremental_forward; with quantize: np.random.choice <- `choice`, or the inverse-CDF draw over `uniforms` (T,), whose
+        probabilities and margins are returned too"""
+        seen = []
+
+        def draw(a, p=None):
+            k, cdf = inv_cdf_draw(p, float(uniforms[len(seen)]))
+            seen.append((np.asarray(p, dtype=np.float32).copy(), float(np.abs(cdf - float(uniforms[len(seen)])).min())))
+            return a[k]
+        np.random.choice = choice if choice is not None else draw
+        try:
+            with torch.no_grad():
+                y = net.incremental_forward(initial_input=None, c=c, g=None, T=T, test_inputs=test_inputs, tqdm=lambda z: z,
+                                            softmax=softmax, quantize=quantize)
+        finally:
+            np.random.choice = real_choice
+        return y, seen
+
+    def rel(a, b):
+        a, b = np.asarray(a, dtype=np.float64).ravel(), np.asarray(b, dtype=np.float64).ravel()
+        return float(np.linalg.norm(a - b) / np.linalg.norm(b))
+
+    checked = False
+    for name, cfg, tag, T, n_tags, need, stride, gains in (("small", W.WNConfigOneHot, "WN.", 64, 120, 1e-4, 1, (4,)),
+                                                           ("deep", WNConfigOneHotDeep, "WNOD.", 160, 40, 3e-5, 4, (4, 8, 16, 32, 64, 128))):
+        K, B = cfg.out_channels, 2
+        c = O.cf_uniform("wnos.%s.c" % name, (B, cfg.cin_channels, T // 16), 0, 1)
+        idx = (O.cf_uniform("wnos.%s.idx" % name, (B, T), 0, 1) * K).long().clamp(max=K - 1)
+        x = torch.nn.functional.one_hot(idx, K).float().transpose(1, 2).contiguous()                   # (B, K, T)
+        for fg in gains:                      # the first-conv gain is raised until what is fed back matters (the deep network is 32 wide)
+            net = make(cfg, tag, fg, 12)
+            p_tf = run(net, c, T, x, True, False)[0].numpy()
+            p_free = run(net, c, T, x[:, :, :4].contiguous(), True, False)[0].numpy()
+            dist = rel(p_free, p_tf)
+            print("  %s: first-conv gain %g: max probability %.3g, free-running vs teacher-forced %.3g" % (name, fg, p_tf.max(), dist))
+            if dist >= 1e-2:
+                break
+        assert dist >= 1e-2, dist
+        l_tf = run(net, c, T, x, False, False)[0].numpy()
+        assert rel(torch.softmax(torch.from_numpy(l_tf), 1).numpy(), p_tf) < 1e-6
+        c1, x1 = c[:1].contiguous(), x[:1, :, :4].contiguous()
+        if not checked:                       # the replacement draws what np.random.choice draws
+            for seed in (3, 11):
+                np.random.seed(seed)
+                want = run(net, c1, T, x1, True, True, choice=real_choice)[0].argmax(1)
+                np.random.seed(seed)
+                got = run(net, c1, T, x1, True, True, uniforms=np.random.random_sample(T))[0].argmax(1)
+                assert torch.equal(want, got), (seed, want, got)
+            checked = True
+        best = None
+        for k in range(n_tags):               # a run whose every draw is clear of the CDF's edges: the search is needed (median margin ~ 2e-5)
+            u = O.cf_uniform("wnos.%s.u%d" % (name, k), (1, T), 0, 1).numpy().reshape(T)
+            y, seen = run(net, c1, T, x1, True, True, uniforms=u)
+            m = min(s[1] for s in seen)
+            if best is None or m > best[0]:
+                best = (m, k, y.argmax(1).numpy().reshape(T), np.stack([s[0] for s in seen]), np.array([s[1] for s in seen]))
+        print("  %s: best of %d uniform tags: %d, margin %.3g" % (name, n_tags, best[1], best[0]))
+        assert best[0] >= need, best[0]
+        steps = np.array([0, 1, T // 2, T - 1], dtype=np.int64)
+        out[name + ".meta"] = np.array([B, T, K, stride, best[1]], dtype=np.int64)
+        out[name + ".gains"] = np.array([fg, 12], dtype=np.float64)
+        out[name + ".p_tf"] = p_tf[:, :, ::stride]
+        out[name + ".logit_steps"] = steps
+        out[name + ".l_tf"] = l_tf[:, :, steps]
+        out[name + ".p_free"] = p_free[:, :, ::stride]
+        out[name + ".feedback_dist"] = np.float64(dist)
+        out[name + ".classes"] = best[2].astype(np.int64)
+        out[name + ".margins"] = best[4]
+        out[name + ".p_samp"] = best[3][::stride]
+    path = os.path.join(OUT, "wavenet_onehot_synth.npz")
+    np.savez_compressed(path, **out)
+    print("wavenet_onehot_synth -> %s (%.1f KB)" % (os.path.relpath(path, ROOT), os.path.getsize(path) / 1024))
+    assert os.path.getsize(path) <= 523767, "larger than the largest fixture"
+
+
 def wavenet_g_goldens():
     """WaveNet with global (speaker) conditioning: teacher-forced forward and incremental_forward from the reference."""
     import Config  # noqa: F401
@@ -1033,6 +1149,9 @@ if __name__ == "__main__":
     if "--wavenet-onehot-only" in sys.argv:
         wavenet_onehot_goldens()
         sys.exit(0)
+    if "--wavenet-onehot-synth-only" in sys.argv:
+        wavenet_onehot_synth_goldens()
+        sys.exit(0)
     if "--ganloss-soft-only" in sys.argv:
         ganloss_soft_goldens()
         sys.exit(0)
@@ -1073,6 +1192,7 @@ if __name__ == "__main__":
     wavenet_g_goldens()
     wavenet_full_goldens()
     wavenet_onehot_goldens()
+    wavenet_onehot_synth_goldens()
     wavenet_deep_goldens()
     av_step_goldens()
     instnorm_goldens()

@@ -22,7 +22,7 @@ class ViaiLibraryError(RuntimeError):
 
 # ABI version THIS file's SIGNATURES / struct mirrors were written against: bumped together with them.  load() compares it with the
 # library, and with the committed header where that is present (a source checkout), so a stale _lib.py cannot call a rebuilt .so.
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 
 def _header_abi_version():
@@ -61,7 +61,9 @@ class WnSynth(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "C", "G", "S", "cin", "n_layers", "out_ch", "T", "n_test")] + [("log_scale_min", C.c_float)] + \
                [("layers", C.POINTER(WnLayer))] + \
                [(n, C.c_void_p) for n in ("w_first", "b_first", "w_l1", "b_l1", "w_l2", "b_l2", "cond", "test_inputs", "u1", "u2",
-                                          "out", "z", "skips", "yhat_dbg", "step", "z2")] + [("fused", C.c_int)]
+                                          "out", "z", "skips", "yhat_dbg", "step", "z2")] + [("fused", C.c_int)] + \
+               [(n, C.c_int) for n in ("categorical", "cat_softmax", "cat_quantize", "init_class")] + \
+               [(n, C.c_void_p) for n in ("w_first_t", "test_classes", "init_rows", "classes")]
 
 
 _P = C.c_void_p
@@ -153,6 +155,8 @@ SIGNATURES = {
     "viai_mol_sample": (_I, [_P, _P, _P, _P, _L, _I, _I, _F, _P]),
     "viai_wavenet_synth_step": (_I, [C.POINTER(WnSynth), _P]),
     "viai_wavenet_synth_run": (_I, [C.POINTER(WnSynth), _I, _I, _P]),
+    "viai_wn_categorical_ok": (_I, [C.POINTER(WnSynth)]),
+    "viai_mulaw_decode": (_I, [_P, _P, _L, _I, _P]),
     "viai_wn_pipe_ok": (_I, [C.POINTER(WnSynth)]),
     "viai_wn_pipe_profile": (_I, [_P, _I]),
     "viai_wn_pipe_image_floats": (C.c_long, [_I]),

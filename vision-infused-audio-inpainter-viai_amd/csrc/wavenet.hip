@@ -723,7 +723,33 @@ __global__ __launch_bounds__(256) void wn_head_generic_kernel(const float* __res
 // layer l - 1 (x_l(t) -> ring_l for the FUTURE time steps' past taps, the running skip sum).  Stage 0 forms x_0(t) = first conv inline.
 // The last layer's skip row product moves into the head.  L + 1 dependent launches per time step; z is double-buffered (stage l
 // writes z_l while its B blocks still read z_{l-1}).  Reassociation only: sums agree with the plain form to fp32 rounding.
+// ---- categorical network (ABI 19): where the input of a time step comes from (wavenet.py:322-327), shared by both chain forms --------------
+// Two forms of the first conv (wavenet.py:116-119, Conv1d1x1(K, C)): the input of stream b is a CLASS k -> x0 = w_t[k] + bias, one contiguous
+// row of the transposed weight; or a DENSE row of K floats -> x0[c] = w[c] . row + bias[c].  The form depends on t and the descriptor only,
+// never on the stream, so every branch on it is uniform over the grid.
+struct WnCatIn {
+    const float* w_t; const float* w;              // [K][C] / [C][K]
+    const int* test_classes; const float* test_rows; const float* init_rows;
+    const int* classes; const float* rows;         // what the previous time steps put out: (B, T) / (B, T, K)
+    int n_test, init_class, quantize, K, T;
+};
+
+__device__ __forceinline__ bool wn_cat_class_form(const WnCatIn& in, int t) {
+    if (t < in.n_test) return in.test_classes != nullptr;
+    if (t > 0) return in.quantize != 0;
+    return in.init_rows == nullptr;
+}
+__device__ __forceinline__ int wn_cat_class(const WnCatIn& in, int t, int b) {
+    const int k = t < in.n_test ? in.test_classes[(size_t)b * in.n_test + t] : (t > 0 ? in.classes[(size_t)b * in.T + t - 1] : in.init_class);
+    return min(max(k, 0), in.K - 1);               // a class from outside (test_classes) never indexes past the weight
+}
+__device__ __forceinline__ const float* wn_cat_row(const WnCatIn& in, int t, int b) {
+    return t < in.n_test ? in.test_rows + ((size_t)b * in.n_test + t) * in.K
+                         : (t > 0 ? in.rows + ((size_t)b * in.T + t - 1) * in.K : in.init_rows + (size_t)b * in.K);
+}
+
 struct WnStage {
+    WnCatIn cat;                                   // categorical network, stage 0 (wn_stage_kernel<NB, true>)
     const float* ring; int ring_len, dil;          // x_l at the past time steps
     const float* ring_prev; int prev_len;          // x_{l-1}, current slot written by stage l - 1 (l > 0)
     const float* w; const float* bias;             // [G][K] extended rows, [G] folded bias
@@ -737,7 +763,9 @@ struct WnStage {
 
 __global__ void wn_tick_kernel(int* step) { *step += 1; }
 
-template <int NB>
+// CAT: the categorical network.  Stage 0 forms x_0(t) from a class by the gather above; a dense input row is a K-long product per channel, which
+// wn_cat_first_kernel does in a launch of its own in front of this stage (ring slot t), and stage 0 reads its current tap from there.
+template <int NB, bool CAT = false>
 __global__ __launch_bounds__(256) void wn_stage_kernel(const WnStage a) {
     __shared__ float red[2 * NB][260];
     const int t = a.t_arg >= 0 ? a.t_arg : *a.step - 1;
@@ -745,6 +773,14 @@ __global__ __launch_bounds__(256) void wn_stage_kernel(const WnStage a) {
     if ((int)blockIdx.x >= H) {
         // ---------------------------------------------------------------- B: what layer l - 1 still owes (or the first conv)
         const int bid = blockIdx.x - H;
+        if (CAT && a.l == 0) {
+            if (wn_cat_class_form(a.cat, t))
+                for (int i = tid; i < NB * C; i += 256) {
+                    const int b = i / C, c = i - b * C;
+                    a.ring_w[((size_t)b * a.ring_len + (t % a.ring_len)) * C + c] = a.cat.w_t[(size_t)wn_cat_class(a.cat, t, b) * C + c] + a.b_first[c];
+                }
+            return;
+        }
         if (a.l == 0) {
             for (int i = tid; i < NB * C; i += 256) {
                 const int b = i / C, c = i - b * C;
@@ -813,7 +849,17 @@ __global__ __launch_bounds__(256) void wn_stage_kernel(const WnStage a) {
                 }
             } else if (k < 3 * C) {                                 // current tap
                 const int ci = k - 2 * C;
-                if (a.l == 0) {                                     // x_0(t): the first conv, formed here
+                if (CAT && a.l == 0) {                              // x_0(t) of the categorical network
+                    if (wn_cat_class_form(a.cat, t)) {
+                        const f32x4 bf = *reinterpret_cast<const f32x4*>(a.b_first + ci);
+#pragma unroll
+                        for (int b = 0; b < NB; ++b) x[b] = *reinterpret_cast<const f32x4*>(a.cat.w_t + (size_t)wn_cat_class(a.cat, t, b) * C + ci) + bf;
+                    } else {
+                        const float* xb = a.ring + (size_t)(t % a.ring_len) * C + ci;
+#pragma unroll
+                        for (int b = 0; b < NB; ++b) x[b] = *reinterpret_cast<const f32x4*>(xb + (size_t)b * a.ring_len * C);
+                    }
+                } else if (a.l == 0) {                              // x_0(t): the first conv, formed here
                     const f32x4 wf = *reinterpret_cast<const f32x4*>(a.w_first + ci), bf = *reinterpret_cast<const f32x4*>(a.b_first + ci);
 #pragma unroll
                     for (int b = 0; b < NB; ++b) {
@@ -1019,6 +1065,154 @@ __global__ __launch_bounds__(256) void wn_head_sample_kernel(const float* __rest
     }
 }
 
+// ---- categorical network: first conv, head rows, softmax + draw ---------------------------------------------------------------------------
+// First conv, a wave per output channel c, every weight row read once for all streams.  Dense form: lane holds 4 of the K <= 256 columns, the
+// wave sum has a fixed order.  Class form: lane b copies one element for stream b (skipped when `dense_only`: the fused stage 0 gathers itself).
+template <int NB>
+__global__ __launch_bounds__(256) void wn_cat_first_kernel(const WnCatIn in, const float* __restrict__ bias, float* __restrict__ ring, int ring_len,
+                                                           const int* __restrict__ step, int t_arg, int C, int dense_only) {
+    const int t = t_arg >= 0 ? t_arg : *step - 1;
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= C) return;
+    const int slot = t % ring_len;
+    if (wn_cat_class_form(in, t)) {
+        if (!dense_only && lane < NB) ring[((size_t)lane * ring_len + slot) * C + c] = in.w_t[(size_t)wn_cat_class(in, t, lane) * C + c] + bias[c];
+        return;
+    }
+    const float bv = bias[c];
+    float acc[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[b] = 0.f;
+    for (int k = lane * 4; k < in.K; k += 256) {
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(in.w + (size_t)c * in.K + k);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const f32x4 xv = *reinterpret_cast<const f32x4*>(wn_cat_row(in, t, b) + k);
+            acc[b] += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const float v = wave_sum_dpp(acc[b]);
+        if (lane == 0) ring[((size_t)b * ring_len + slot) * C + c] = v + bv;
+    }
+}
+
+// a 1x1 layer of the head over all streams: out[b][o] = act(w[o] . relu(x[b]) + bias[o]); a wave per row o (wavenet.py:133-138: ReLU, 1x1, ReLU, 1x1)
+template <int NB>
+__global__ __launch_bounds__(256) void wn_cat_rows_kernel(const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ x, int K,
+                                                          float* __restrict__ out, int nrows, int relu_out) {
+    const int o = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (o >= nrows) return;
+    const float bv = bias[o];
+    float acc[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[b] = 0.f;
+    for (int k = lane * 4; k < K; k += 256) {
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(w + (size_t)o * K + k);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + (size_t)b * K + k);
+            acc[b] += fmaxf(xv[0], 0.f) * wv[0] + fmaxf(xv[1], 0.f) * wv[1] + fmaxf(xv[2], 0.f) * wv[2] + fmaxf(xv[3], 0.f) * wv[3];
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const float v = wave_sum_dpp(acc[b]) + bv;
+        if (lane == 0) out[(size_t)b * nrows + o] = relu_out ? fmaxf(v, 0.f) : v;
+    }
+}
+
+// softmax over the K <= 256 logits of stream b = blockIdx.x (thread = class) and the categorical draw (wavenet.py:351-356).
+//   softmax: p = exp(x - max) / sum, fp32 (F.softmax)
+//   draw:    np.random.choice(K, p) from one uniform u: cdf = cumsum(p) (numpy: in fp64) / cdf[K - 1]; class = #{k: cdf[k] <= u}
+//            (searchsorted side = "right"), at most K - 1.  The prefix sum is a wave64 scan plus a carry over the four waves added in wave order.
+__global__ __launch_bounds__(256) void wn_cat_sample_kernel(const float* __restrict__ logits, const float* __restrict__ u, int* __restrict__ classes,
+                                                            float* __restrict__ rows, const int* __restrict__ step, int t_arg, int K, int T,
+                                                            int softmax, int quantize) {
+    __shared__ float red[4];
+    __shared__ double carry[4];
+    __shared__ int cnt[4];
+    const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int t = t_arg >= 0 ? t_arg : *step - 1;
+    const bool live = tid < K;
+    const float x = live ? logits[(size_t)b * K + tid] : -INFINITY;
+    const float uu = quantize ? u[(size_t)b * T + t] : 0.f;
+    float* row = rows ? rows + ((size_t)b * T + t) * K : nullptr;
+    if (!softmax) {
+        if (row && live) row[tid] = x;
+        return;
+    }
+    float m = x;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const float e = live ? expf(x - m) : 0.f;
+    const float p = e / block_sum(e, red);                          // block_sum's first barrier also fences the reads of red above
+    if (!quantize) {
+        if (row && live) row[tid] = p;
+        return;
+    }
+    double v = (double)p;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double n = __shfl_up(v, o, 64);
+        if (lane >= o) v += n;
+    }
+    if (lane == 63) carry[wave] = v;
+    __syncthreads();
+    double pre = 0.0;
+    for (int w = 0; w < wave; ++w) pre += carry[w];
+    const double total = ((carry[0] + carry[1]) + carry[2]) + carry[3];
+    const double cdf = (pre + v) / total;
+    const unsigned long long below = __ballot(live && cdf <= (double)uu);
+    if (lane == 0) cnt[wave] = __popcll(below);
+    __syncthreads();
+    const int cls = min(cnt[0] + cnt[1] + cnt[2] + cnt[3], K - 1);
+    if (tid == 0) classes[(size_t)b * T + t] = cls;
+    if (row && live) row[tid] = tid == cls ? 1.f : 0.f;             // wavenet.py:355-356
+}
+
+__global__ __launch_bounds__(256) void mulaw_decode_kernel(const int* __restrict__ cls, float* __restrict__ out, long n, float mu) {
+    const float l1p = log1pf(mu);
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
+        const float y = 2.f * (float)cls[i] / mu - 1.f;
+        const float mag = expm1f(fabsf(y) * l1p) / mu;              // ((1 + mu)^|y| - 1) / mu
+        out[i] = y < 0.f ? -mag : mag;
+    }
+}
+
+WnCatIn wn_cat_in(const viai_wn_synth* s) {
+    WnCatIn in{};
+    in.w_t = s->w_first_t; in.w = s->w_first; in.test_classes = s->test_classes; in.test_rows = s->test_inputs; in.init_rows = s->init_rows;
+    in.classes = s->classes; in.rows = s->yhat_dbg; in.n_test = s->n_test; in.init_class = s->init_class; in.quantize = s->cat_quantize;
+    in.K = s->out_ch; in.T = s->T;
+    return in;
+}
+
+// host copy of wn_cat_class_form; t < 0 (time index on the device): "may a dense step occur at all"
+bool wn_cat_dense_at(const viai_wn_synth* s, int t) {
+    if (t < 0) return (s->n_test > 0 && s->test_classes == nullptr) || !s->cat_quantize || (s->n_test == 0 && s->init_rows != nullptr);
+    if (t < s->n_test) return s->test_classes == nullptr;
+    if (t > 0) return !s->cat_quantize;
+    return s->init_rows != nullptr;
+}
+
+// the output end of a categorical time step: the head's two 1x1 layers over all streams (hidden layer and logits in the scratch `out`), then
+// softmax + draw, a block per stream.  `skips` holds the finished skip sum (the ReLU in front of W1 is applied on the read).
+template <int NB>
+void wn_cat_head(const viai_wn_synth* s, int t_arg, hipStream_t st) {
+    const int S = s->S, K = s->out_ch;
+    float* hid = s->out;
+    float* logits = s->out + (size_t)s->B * S;
+    VIAI_LAUNCH(wn_cat_rows_kernel<NB>, dim3((S + 3) / 4), dim3(256), 0, st, s->w_l1, s->b_l1, (const float*)s->skips, S, hid, S, 1);
+    VIAI_LAUNCH(wn_cat_rows_kernel<NB>, dim3((K + 3) / 4), dim3(256), 0, st, s->w_l2, s->b_l2, (const float*)hid, S, logits, K, 0);
+    VIAI_LAUNCH(wn_cat_sample_kernel, dim3(s->B), dim3(256), 0, st, (const float*)logits, s->u2, s->classes, s->yhat_dbg, s->step, t_arg, K, s->T,
+                s->cat_softmax, s->cat_quantize);
+}
+
 bool wn_fused_ok(const viai_wn_synth* s) {
     if (!s->fused || s->z2 == nullptr) return false;
     if (s->S > 256 || s->out_ch > 256 || s->G / 2 > 256) return false;
@@ -1031,6 +1225,9 @@ int wn_step_fused_impl(const viai_wn_synth* s, int t_arg, hipStream_t st) {
     const int C = s->C, H = s->G / 2, S = s->S, n = s->n_layers;
     const viai_wn_layer* L = s->layers;
     if (t_arg < 0) VIAI_LAUNCH(wn_tick_kernel, dim3(1), dim3(1), 0, st, s->step);
+    const bool cat = s->categorical != 0;
+    if (cat && wn_cat_dense_at(s, t_arg))
+        VIAI_LAUNCH(wn_cat_first_kernel<NB>, dim3((C + 3) / 4), dim3(256), 0, st, wn_cat_in(s), s->b_first, L[0].ring, L[0].ring_len, s->step, t_arg, C, 1);
     float* zb[2] = {s->z, s->z2};
     for (int l = 0; l < n; ++l) {
         WnStage a{};
@@ -1046,7 +1243,17 @@ int wn_step_fused_impl(const viai_wn_synth* s, int t_arg, hipStream_t st) {
         }
         a.step = s->step; a.t_arg = t_arg; a.l = l; a.C = C; a.H = H; a.S = S; a.cin = s->cin; a.T = s->T; a.B = s->B;
         const int nb = H + (l == 0 ? 1 : (C + S + 3) / 4);
-        VIAI_LAUNCH(wn_stage_kernel<NB>, dim3(nb), dim3(256), 0, st, a);
+        if (cat && l == 0) {
+            a.cat = wn_cat_in(s);
+            VIAI_LAUNCH((wn_stage_kernel<NB, true>), dim3(nb), dim3(256), 0, st, a);
+        } else {
+            VIAI_LAUNCH(wn_stage_kernel<NB>, dim3(nb), dim3(256), 0, st, a);
+        }
+    }
+    if (cat) {                                     // the last layer's skip rows (in place), then the categorical head
+        VIAI_LAUNCH(wn_head_rows_kernel<NB>, dim3((S + 3) / 4), dim3(256), 0, st, L[n - 1].w_skip, L[n - 1].b_skip, (const float*)zb[(n - 1) & 1], H, s->skips, S, 0, n == 1 ? 1 : 0);
+        wn_cat_head<NB>(s, t_arg, st);
+        return viai_launch_status();
     }
     if (S <= H && s->out_ch <= 256) {
         float* zlast = zb[(n - 1) & 1];
@@ -1067,6 +1274,10 @@ template <int NB>
 int wn_step_impl(const viai_wn_synth* s, int t_arg, hipStream_t st) {
     const int C = s->C, H = s->G / 2, S = s->S;
     const viai_wn_layer* L = s->layers;
+    if (s->categorical) {                          // several blocks: the time index is advanced by a launch of its own, as in the fused form
+        if (t_arg < 0) VIAI_LAUNCH(wn_tick_kernel, dim3(1), dim3(1), 0, st, s->step);
+        VIAI_LAUNCH(wn_cat_first_kernel<NB>, dim3((C + 3) / 4), dim3(256), 0, st, wn_cat_in(s), s->b_first, L[0].ring, L[0].ring_len, s->step, t_arg, C, 0);
+    } else
     VIAI_LAUNCH(wn_first_kernel, dim3(1), dim3(256), 0, st, s->w_first, s->b_first, s->test_inputs, s->n_test, s->out,
                 L[0].ring, L[0].ring_len, s->step, t_arg, s->B, C, s->T);
     for (int l = 0; l < s->n_layers; ++l) {
@@ -1076,6 +1287,10 @@ int wn_step_impl(const viai_wn_synth* s, int t_arg, hipStream_t st) {
         VIAI_LAUNCH(wn_out_kernel<NB>, dim3((C + S + 3) / 4), dim3(256), 0, st, s->z, L[l].w_out, L[l].b_out, L[l].w_skip, L[l].b_skip,
                     L[l].ring, L[l].ring_len, last ? (float*)nullptr : L[l + 1].ring, last ? 1 : L[l + 1].ring_len, s->skips, l == 0 ? 1 : 0,
                     s->step, t_arg, C, H, S);
+    }
+    if (s->categorical) {
+        wn_cat_head<NB>(s, t_arg, st);
+        return viai_launch_status();
     }
     if (S <= 256 && s->out_ch <= 256)
         VIAI_LAUNCH(wn_head_kernel, dim3(s->B), dim3(1024), (2 * S + ((s->out_ch + 3) & ~3) + s->out_ch / 3 + 1) * sizeof(float), st, s->skips, s->w_l1, s->b_l1, s->w_l2, s->b_l2,
@@ -1087,7 +1302,13 @@ int wn_step_impl(const viai_wn_synth* s, int t_arg, hipStream_t st) {
 }
 
 bool wn_valid(const viai_wn_synth* s) {
-    return s && s->B >= 1 && s->B <= WN_MAXB && s->C % 4 == 0 && (s->G / 2) % 4 == 0 && s->cin % 4 == 0 && s->S % 4 == 0 && s->out_ch % 3 == 0 && s->n_layers >= 1;
+    if (!s || s->B < 1 || s->B > WN_MAXB || s->C % 4 != 0 || (s->G / 2) % 4 != 0 || s->cin % 4 != 0 || s->S % 4 != 0 || s->n_layers < 1) return false;
+    if (!s->categorical) return s->out_ch % 3 == 0;             // [logit | mean | log_scale] x nr_mix: the mixture-of-logistics head only
+    if (!viai_wn_categorical_ok(s)) return false;
+    if (s->w_first == nullptr || s->w_first_t == nullptr || s->out == nullptr) return false;
+    if (s->n_test > 0 && s->test_classes == nullptr && s->test_inputs == nullptr) return false;
+    if (s->cat_quantize ? (s->classes == nullptr || s->u2 == nullptr) : s->yhat_dbg == nullptr) return false;
+    return true;
 }
 
 int wn_step(const viai_wn_synth* s, int t_arg, hipStream_t st) {
@@ -1110,6 +1331,23 @@ int wn_step(const viai_wn_synth* s, int t_arg, hipStream_t st) {
 }
 
 }  // namespace
+
+extern "C" int viai_wn_categorical_ok(const viai_wn_synth* s) {
+    if (!s || !s->categorical) return 0;
+    if (s->B != 1 && s->B != 2 && s->B != 4 && s->B != 8) return 0;
+    if (s->out_ch < 4 || s->out_ch > 256 || s->out_ch % 4 != 0) return 0;
+    if (s->C < 4 || s->C % 4 != 0 || s->G < 8 || (s->G / 2) % 4 != 0 || s->cin % 4 != 0 || s->S < 4 || s->S % 4 != 0 || s->n_layers < 1) return 0;
+    if (s->cat_quantize && !s->cat_softmax) return 0;           // logits are no probabilities (wavenet.py:351-354 raises there)
+    if (s->init_class < 0 || s->init_class >= s->out_ch) return 0;
+    return 1;
+}
+
+extern "C" int viai_mulaw_decode(const int* classes, float* out, long n, int mu, void* stream) {
+    if (n < 0 || mu < 1) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    VIAI_LAUNCH(mulaw_decode_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, classes, out, n, (float)mu);
+    return viai_launch_status();
+}
 
 extern "C" int viai_wavenet_synth_step(const viai_wn_synth* s, void* stream) {
     if (!wn_valid(s)) return (int)hipErrorInvalidValue;

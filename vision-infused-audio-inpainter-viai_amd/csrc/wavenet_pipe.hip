@@ -571,6 +571,7 @@ constexpr size_t PIPE_LDS_BYTES = (size_t)((GROWS + BROWS) * LROW + KPRE + PC + 
 // ---- C ABI ------------------------------------------------------------------------------------------------------------------------
 extern "C" int viai_wn_pipe_ok(const viai_wn_synth* s) {
     if (!s || s->C != PC || s->G != 2 * PH || s->S != PS || s->cin != PCIN || s->n_layers != NL || s->out_ch != 30 || s->out_ch % 3 != 0) return 0;
+    if (s->categorical) return 0;                                // one-hot / softmax network: the chain forms only (csrc/wavenet.hip)
     if (s->B < 1 || s->B > PIPE_MAXB || s->cond == nullptr) return 0;
     for (int l = 0; l < NL; ++l) {
         if (s->layers[l].g_add != nullptr || s->layers[l].w_stage == nullptr || s->layers[l].w_c == nullptr) return 0;

@@ -253,6 +253,18 @@ def to_one_hot(tensor, n, fill_with=1.):
     return out.scatter_(tensor.dim(), tensor.long().unsqueeze(-1), fill_with)
 
 
+def mulaw_decode(classes, mu=255):
+    """mu-law classes (integer tensor, any shape, on the GPU) -> waveform in [-1, 1]: y = 2 k / mu - 1, x = sign(y) ((1 + mu)^|y| - 1) / mu,
+    the inverse of the `mulaw_quantize` of the reference's data preparation (utils/librivox.py:66-68; the reference decodes with nnmnkwii's
+    `inv_mulaw_quantize`, utils/model_util.py:63-64).  HIP kernel `viai_mulaw_decode`."""
+    lib = _lib.load()
+    k = classes.to(torch.int32).contiguous()
+    out = torch.empty(k.shape, dtype=torch.float32, device=k.device)
+    _lib.check(lib.viai_mulaw_decode(k.data_ptr(), out.data_ptr(), k.numel(), int(mu), torch.cuda.current_stream().cuda_stream),
+               "viai_mulaw_decode")
+    return out
+
+
 # ----------------------------------------------------------------------------- modules
 def _wn(m, on):
     return nn.utils.weight_norm(m) if on else m
@@ -456,8 +468,20 @@ class WaveNet(nn.Module):
 
     @torch.no_grad()
     def incremental_forward(self, initial_input=None, c=None, g=None, T=100, test_inputs=None, tqdm=lambda x: x, softmax=True,
-                            quantize=True, log_scale_min=-7.0, uniforms=None, use_graph=False, return_logits=False, timing=None):
-        """Sample-by-sample synthesis (wavenet.py:237-364) for the scalar-input / MoL configuration.
+                            quantize=True, log_scale_min=-7.0, uniforms=None, use_graph=False, return_logits=False, timing=None,
+                            return_classes=False, input_form="auto"):
+        """Sample-by-sample synthesis (wavenet.py:237-364), both configurations of the reference.
+
+        scalar_input=False (one-hot mu-law input, softmax over K = out_channels classes; chain forms only): returns (B, K, T) like the reference --
+        softmax / quantize True / True: the one-hot rows of the sampled classes, the class fed back; True / False: the probabilities, fed back as
+        they are; False / False: the logits; False / True raises ValueError (the reference hands logits to np.random.choice, which raises).
+        `uniforms=` (B, T) draws in [0, 1), one per stream and step, used at every step (teacher-forced ones too, as the reference's
+        np.random.choice is); default torch.rand.  Every stream draws its own class (the reference's quantize=True works for B = 1 only).
+        `return_classes=True` (with quantize): the (B, T) int64 classes, the (B, K, T) one-hot tensor is never formed.  `test_inputs` /
+        `initial_input` in either layout, (B, K, n) or (B, n, K); teacher-forced rows that are exactly one-hot go through the class form of
+        the first conv (a row gather), anything else -- or everything, with input_form="dense" -- through the dense form (a K-long product).
+
+        scalar_input=True (mixture of logistics):
 
         A time step = first conv, 2 GEMV-batch kernels per layer, head + MoL sample.  Default: `viai_wavenet_synth_run` loops over the
         steps in C with the time index passed by value; `use_graph=True`: `viai_wavenet_synth_step` (time index on the device, the first
@@ -466,20 +490,42 @@ class WaveNet(nn.Module):
         `timing={"warmup": W}` (bench.py): the first W time steps run untimed, the remaining T - W are bracketed by device
         synchronisations and reported as timing["ms"] / timing["steps"] (set-up -- weight norm, linearised weights -- excluded)."""
         import ctypes as Ct
+        cat = not self.scalar_input
+        K = self.out_channels
+        if cat:
+            if quantize and not softmax:
+                raise ValueError("incremental_forward: quantize=True needs softmax=True (logits are no probabilities to draw a class from)")
+            if return_logits:
+                raise ValueError("incremental_forward: return_logits belongs to the mixture-of-logistics network; softmax=False, quantize=False returns the logits")
+            if return_classes and not quantize:
+                raise ValueError("incremental_forward: return_classes needs quantize=True")
+            if input_form not in ("auto", "dense"):
+                raise ValueError("incremental_forward: input_form is 'auto' or 'dense'")
         lib = _lib.load()
-        if not self.scalar_input:
-            raise NotImplementedError("incremental_forward: scalar-input (mixture of logistics) WaveNet only")
         dev = self.first_conv.bias.device
+        tcls = init_rows = None
         if test_inputs is not None:
-            if test_inputs.size(1) == 1:
-                test_inputs = test_inputs.transpose(1, 2)                             # -> (B, n, 1)
+            if test_inputs.size(1) == (K if cat else 1):
+                test_inputs = test_inputs.transpose(1, 2)                             # -> (B, n, K) / (B, n, 1)  (wavenet.py:268-274)
             B = test_inputs.size(0)
             T = test_inputs.size(1) if T is None else max(int(T), test_inputs.size(1))
-            tin = test_inputs.reshape(B, -1).to(dev).float().contiguous()
+            if cat:
+                tin = test_inputs.to(dev).float().contiguous()                        # (B, n, K)
+                assert tin.size(2) == K, "test_inputs: (B, K, n) or (B, n, K)"
+                if input_form == "auto" and bool((((tin == 0) | (tin == 1)).all(-1) & (tin.sum(-1) == 1)).all()):
+                    tcls = tin.argmax(-1).to(torch.int32).contiguous()                # exactly one-hot rows: the class form
+            else:
+                tin = test_inputs.reshape(B, -1).to(dev).float().contiguous()
         else:
-            B = c.size(0) if c is not None else 1
+            B = c.size(0) if c is not None else (initial_input.size(0) if (cat and initial_input is not None) else 1)
             tin = None
         T = int(T)
+        if cat and initial_input is None and tin is None and K <= 127:
+            raise ValueError("incremental_forward: the default initial input is class 127 (wavenet.py:308-312); with %d classes pass initial_input" % K)
+        if cat and initial_input is not None:                                         # wavenet.py:316-318
+            if initial_input.size(1) == K:
+                initial_input = initial_input.transpose(1, 2)
+            init_rows = initial_input.to(dev).float().reshape(B, K).contiguous()
         if not 1 <= B <= 32:
             raise NotImplementedError("incremental_forward: 1 to 32 streams")
         cond = None
@@ -487,7 +533,10 @@ class WaveNet(nn.Module):
             cu = self._upsample(c.to(dev).float())
             assert cu.size(-1) == T
             cond = cu.transpose(1, 2).contiguous()                                    # (B, T, cin)
-        if uniforms is None:
+        if cat:
+            u1 = None
+            u2 = torch.rand(B, T, device=dev) if uniforms is None else uniforms.to(dev).float().reshape(B, T).contiguous()
+        elif uniforms is None:
             u1 = torch.empty(B, T, self.out_channels // 3, device=dev).uniform_(1e-5, 1.0 - 1e-5)
             u2 = torch.empty(B, T, device=dev).uniform_(1e-5, 1.0 - 1e-5)
         else:
@@ -548,8 +597,10 @@ class WaveNet(nn.Module):
             # computed once per layer by the HIP 1x1 conv and handed to the step kernel as a per-stream constant
             L.g_add = (t(conv1d_apply(g_vec.transpose(1, 2).reshape(B, 1, 1, -1).contiguous(), f.conv1x1g).reshape(B, G))
                        if (g_vec is not None and f.conv1x1g is not None) else None)
-        out = torch.zeros(B, T, device=dev)
-        logits = torch.zeros(B, T, self.out_channels, device=dev) if return_logits else None
+        # categorical network: `out` is the head's scratch (hidden layer, logits), `logits` the (B, T, K) rows of the reference's `outputs`
+        out = torch.zeros(B, S + K, device=dev) if cat else torch.zeros(B, T, device=dev)
+        logits = torch.zeros(B, T, self.out_channels, device=dev) if (return_logits or (cat and not return_classes)) else None
+        classes = torch.zeros(B, T, dtype=torch.int32, device=dev) if cat else None
         z = torch.zeros(B, G // 2, device=dev)
         z2 = torch.zeros(B, G // 2, device=dev)
         skips = torch.zeros(B, S, device=dev)
@@ -559,12 +610,18 @@ class WaveNet(nn.Module):
         st.n_test = tin.size(1) if tin is not None else 0
         st.log_scale_min = float(log_scale_min)
         st.layers = layers
-        st.w_first, st.b_first = t(normed_weight(self.first_conv).reshape(-1)), t(self.first_conv.bias)
+        st.w_first, st.b_first = t(normed_weight(self.first_conv).reshape(-1)), t(self.first_conv.bias)      # categorical: [C][K]
+        if cat:
+            st.categorical, st.cat_softmax, st.cat_quantize, st.init_class = 1, int(bool(softmax)), int(bool(quantize)), 127 if K > 127 else 0
+            st.w_first_t = t(normed_weight(self.first_conv).reshape(Cc, K).t())                              # [K][C]: a class is one row
+            st.test_classes = tcls.data_ptr() if tcls is not None else None
+            st.init_rows = init_rows.data_ptr() if init_rows is not None else None
+            st.classes = classes.data_ptr()
         st.w_l1, st.b_l1 = t(normed_weight(self.last_conv_layers[1]).reshape(S, -1)), t(self.last_conv_layers[1].bias)
         st.w_l2, st.b_l2 = t(normed_weight(self.last_conv_layers[3]).reshape(self.out_channels, -1)), t(self.last_conv_layers[3].bias)
         st.cond = cond.data_ptr() if cond is not None else None
         st.test_inputs = tin.data_ptr() if tin is not None else None
-        st.u1, st.u2, st.out, st.z, st.skips, st.step = u1.data_ptr(), u2.data_ptr(), out.data_ptr(), z.data_ptr(), skips.data_ptr(), step.data_ptr()
+        st.u1, st.u2, st.out, st.z, st.skips, st.step = (u1.data_ptr() if u1 is not None else None), u2.data_ptr(), out.data_ptr(), z.data_ptr(), skips.data_ptr(), step.data_ptr()
         st.yhat_dbg = logits.data_ptr() if logits is not None else None
         st.z2, st.fused = z2.data_ptr(), 1 if fuse else 0
         ref = Ct.byref(st)
@@ -574,6 +631,8 @@ class WaveNet(nn.Module):
         if not pipe and B not in (1, 2, 4, 8):
             raise NotImplementedError("incremental_forward: the chain of launches takes 1, 2, 4 or 8 streams; any other count up to 32 needs the pipelined form "
                                       "(reference-size network, local conditioning only, no use_graph, VIAI_WN_PIPE != 0, a device with 256 compute units)")
+        if cat and not lib.viai_wn_categorical_ok(ref):
+            raise NotImplementedError("incremental_forward: the one-hot network needs out_channels <= 256 and a multiple of 4, channel counts that are multiples of 4")
         if pipe:
             imgs = _pipe_images(held["w_stage"], held["b_stage"], held["w_c"], held["w_out"], held["b_out"], held["w_skip"], held["b_skip"],
                                 normed_weight(self.last_conv_layers[1]).reshape(S, -1).detach().float(), self.last_conv_layers[1].bias.detach().float(),
@@ -633,6 +692,10 @@ class WaveNet(nn.Module):
                 timing["ms"], timing["steps"] = (time.perf_counter() - t_start) * 1e3, T - w0
         torch.cuda.current_stream().synchronize()
         del keep
+        if cat:
+            if return_classes:
+                return classes.long()
+            return logits.transpose(1, 2).contiguous()                                # (B, K, T) like the reference (wavenet.py:358-361)
         res = out.unsqueeze(1)                                                        # (B, 1, T) like the reference
         return (res, logits) if return_logits else res
 
