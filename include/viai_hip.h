@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VIAI_ABI_VERSION 19
+#define VIAI_ABI_VERSION 20
 
 enum { VIAI_ACT_NONE = 0, VIAI_ACT_RELU = 1, VIAI_ACT_LRELU = 2, VIAI_ACT_SIGMOID = 3 };
 
@@ -371,6 +371,30 @@ int viai_wn_categorical_ok(const viai_wn_synth* s);
 /* mu-law classes -> waveform in [-1, 1]: y = 2 k / mu - 1, x = sign(y) ((1 + mu)^|y| - 1) / mu (the inverse of the mulaw_quantize the reference's
  * data preparation applies, utils/librivox.py:66-68; decoded there by utils/model_util.py:63-64); classes, out: n elements */
 int viai_mulaw_decode(const int* classes, float* out, long n, int mu, void* stream);
+/* waveform in [-1, 1] -> mu-law classes, the inverse of viai_mulaw_decode (ABI v20): y = sign(x) log1p(mu |x|) / log1p(mu),
+ * class = trunc((y + 1) / 2 * mu) clamped to [0, mu] -- the closed form of the `P.mulaw_quantize` the reference's data preparation calls
+ * (utils/librivox.py:66-74); x, classes: n elements */
+int viai_mulaw_quantize(const float* x, int* classes, long n, int mu, void* stream);
+
+/* ---- training the categorical network from class indices (ABI v20) ----
+ * MaskedCrossEntropyLoss (loss_functions.py:24-40) on logits as rows: logits[B * T][pitch], pitch >= K, K % 4 == 0, pitch % 4 == 0 -- the NHWC
+ * tensor of the network's last conv, no transpose.  target: B * T int32 classes.  With shift = s the logits row t of a stream is scored against
+ * target t + s for t < T - s and the last s rows of every stream carry zero weight and zero gradient: the training convention
+ * criterion(y_hat[:, :, :-1], y[:, 1:]) (train.py's __train_step) without a sliced copy.  mask (optional): B * (T - s) floats, mask[b][t]
+ * weighs logits row t.  loss = sum(l * mask) / sum(mask), summed in a fixed order.  loss_rows: [B * T]; wrow: [2 * B * T] scratch (the
+ * normalised row weights mask / sum(mask), then the mask as applied); dlogits (optional, rows of `pitch` floats) = d loss / d logits with
+ * zeros in the columns K .. pitch.  The target logit is picked by comparing column numbers, never by addressing with the target: a target
+ * outside [0, K) gives a NaN row loss where the row's mask is not 0 and is ignored where it is 0.                                        */
+int viai_masked_ce_loss(const float* logits, const int* target, const float* mask, float* loss_rows, float* wrow, float* loss,
+                        float* dlogits, int B, int T, int K, int pitch, int shift, void* stream);
+/* first_conv of the categorical network on class indices (wavenet.py:118 applied to the one-hot rows of data_loader_utils.py:278-281):
+ * h[p][:] = w[:, classes[p]] + b.  w: the layer's effective weight [C][K]; wt: [K][C] scratch that receives its transposed image (written
+ * by this call, once per forward); classes: `rows` int32; h: [rows][C]; C % 4 == 0.  A class outside [0, K) gives a NaN row, not an access. */
+int viai_class_embed_fwd(const int* classes, const float* w, const float* b, float* wt, float* h, long rows, int K, int C, void* stream);
+/* its weight gradients, in the parameter's layout: dw[c][k] = sum over rows p with classes[p] == k of dh[p][c] (ascending p), db[c] = sum_k
+ * dw[c][k].  No float atomics: the same bits on every run.  part: K * C * viai_class_embed_bwd_segments(rows) floats of scratch; C <= 1024. */
+int viai_class_embed_bwd_segments(long rows);
+int viai_class_embed_bwd(const float* dh, const int* classes, float* part, float* dw, float* db, long rows, int K, int C, void* stream);
 /* The same time steps t0 .. t0 + n_steps - 1 launched from a host loop with the time index passed BY VALUE (ABI v5): no kernel starts
  * with a load of `*step` in front of its address arithmetic (a full memory round trip at these grid sizes).  `step` is not touched.
  * wavenet.py:237-364 incremental_forward's loop body, n_steps at a time.                                                         */

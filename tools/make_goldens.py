@@ -687,6 +687,81 @@ def wavenet_onehot_synth_goldens():
     assert os.path.getsize(path) <= 523767, "larger than the largest fixture"
 
 
+class WNConfigOneHotFull:
+    """oracle/wavenet_oracle.py's WNConfigFull (the reference's size: 24 layers / 4 stacks / 512 residual + gate / 256 skip channels, hop 256) with
+    one-hot input and 256 classes.  tests/test_wavenet_onehot_train_gpu.py restates it."""
+    out_channels, layers, stacks, residual_channels, gate_channels, skip_out_channels = 256, 24, 4, 512, 512, 256
+    kernel_size, cin_channels, upsample_scales, freq_axis_kernel_size, gin_channels, n_speakers = 3, 80, (4, 4, 4, 4), 3, -1, None
+    scalar_input = False
+
+
+def masked_ce_fp64(yh, tgt, mask):
+    """MaskedCrossEntropyLoss restated in fp64: yh (B, K, T'), tgt (B, T') classes, mask (B, T') -> sum(ce * mask) / sum(mask)"""
+    ce = torch.nn.functional.cross_entropy(yh.double(), tgt.long(), reduction="none")
+    return (ce * mask.double()).sum() / mask.double().sum()
+
+
+def wavenet_onehot_train_goldens():
+    """Training step of the one-hot (mu-law, 256-way softmax) WaveNet from the reference's own `WaveNet(scalar_input=False)` and
+    `MaskedCrossEntropyLoss` (loss_functions.py:24-40) under the training convention of train.py's __train_step:
+    criterion(y_hat[:, :, :-1].unsqueeze(-1), y[:, 1:], lengths=..., max_len=T - 1), where y holds the classes of the input itself (the network
+    predicts its next sample).  Lengths are (T, T - 14) less the one step the convention drops, so the mask leaves rows out; the reference-width
+    case has one stream, the shorter one.  Small case: outputs, loss and five gradients; reference-width case: digests only."""
+    import Config  # noqa: F401
+    from oracle import wavenet_oracle as W
+    from wavenet_vocoder import wavenet as RW
+    import warnings
+    out = OrderedDict()
+    for name, cfg, tag, B, T in (("small", W.WNConfigOneHot, "WN.", 2, 64), ("full", WNConfigOneHotFull, "WNOF.", 1, 1024)):
+        K = cfg.out_channels
+        net = RW.WaveNet(out_channels=K, layers=cfg.layers, stacks=cfg.stacks, residual_channels=cfg.residual_channels,
+                         gate_channels=cfg.gate_channels, skip_out_channels=cfg.skip_out_channels, kernel_size=cfg.kernel_size, dropout=0.0,
+                         cin_channels=cfg.cin_channels, gin_channels=-1, n_speakers=None, weight_normalization=True,
+                         upsample_conditional_features=True, upsample_scales=list(cfg.upsample_scales),
+                         freq_axis_kernel_size=cfg.freq_axis_kernel_size, scalar_input=False)
+        sd = W.wavenet_state(cfg, tag)
+        assert list(net.state_dict().keys()) == list(sd.keys())
+        load_into(net, sd)
+        net.train()
+        hop = int(np.prod(cfg.upsample_scales))
+        idx = (O.cf_uniform("wnot.%s.idx" % name, (B, T), 0, 1) * K).long().clamp(max=K - 1)
+        x = torch.nn.functional.one_hot(idx, K).float().transpose(1, 2).contiguous()                   # (B, K, T)  data_loader_utils.py:278-281
+        c = O.cf_uniform("wnot.%s.c" % name, (B, cfg.cin_channels, T // hop), 0, 1)
+        y = idx.unsqueeze(-1)                                                                          # (B, T, 1)
+        lengths = torch.tensor([T - 1, T - 15][2 - B:], dtype=torch.long)
+        yh = net(x, c)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")                                                            # reduce=False is deprecated, not gone
+            loss = RefLoss.MaskedCrossEntropyLoss()(yh[:, :, :-1].unsqueeze(-1), y[:, 1:], lengths=lengths, max_len=T - 1)
+        loss.backward()
+        mask = RefLoss.sequence_mask(lengths, T - 1)
+        assert 0 < mask.sum().item() < B * (T - 1)
+        with torch.no_grad():
+            oyh = W.wavenet_forward(sd, x, c, cfg)
+            oloss = masked_ce_fp64(oyh[:, :, :-1], idx[:, 1:], mask)
+        assert relerr(oyh, yh) < 1e-5, relerr(oyh, yh)
+        assert abs(oloss.item() - loss.item()) < 1e-5 * abs(loss.item()), (oloss.item(), loss.item())
+        params = dict(net.named_parameters())
+        out[name + ".meta"] = np.array([B, T, K], dtype=np.int64)
+        out[name + ".lengths"] = lengths.numpy()
+        out[name + ".loss"] = np.float64(loss.item())
+        if name == "small":
+            out[name + ".idx"] = idx.numpy()
+            out[name + ".yhat"] = yh.detach().numpy()
+            for k in ("first_conv.weight_v", "first_conv.weight_g", "conv_layers.2.conv.weight_v", "last_conv_layers.3.weight_v", "last_conv_layers.3.bias"):
+                out["%s.g.%s" % (name, k)] = params[k].grad.numpy().copy()
+        else:
+            out[name + ".yhat.dg"] = O.digest(yh, 256)
+            for k in ("first_conv.weight_v", "first_conv.weight_g", "first_conv.bias", "conv_layers.0.conv.weight_v", "conv_layers.11.conv.weight_g",
+                      "conv_layers.23.conv.weight_v", "conv_layers.12.conv1x1_skip.bias", "last_conv_layers.1.weight_v", "last_conv_layers.3.weight_v",
+                      "last_conv_layers.3.bias", "upsample_conv.0.weight_v"):
+                out["%s.g.%s.dg" % (name, k)] = O.digest(params[k].grad)
+        print("  %s: loss %.6f, mask %d of %d rows" % (name, loss.item(), int(mask.sum().item()), B * (T - 1)))
+    path = os.path.join(OUT, "wavenet_onehot_train.npz")
+    np.savez_compressed(path, **out)
+    print("wavenet_onehot_train -> %s (%.1f KB)" % (os.path.relpath(path, ROOT), os.path.getsize(path) / 1024))
+
+
 def wavenet_g_goldens():
     """WaveNet with global (speaker) conditioning: teacher-forced forward and incremental_forward from the reference."""
     import Config  # noqa: F401
@@ -1152,6 +1227,10 @@ if __name__ == "__main__":
     if "--wavenet-onehot-synth-only" in sys.argv:
         wavenet_onehot_synth_goldens()
         sys.exit(0)
+    if "--wavenet-onehot-train-only" in sys.argv:
+        torch.set_num_threads(os.cpu_count())
+        wavenet_onehot_train_goldens()
+        sys.exit(0)
     if "--ganloss-soft-only" in sys.argv:
         ganloss_soft_goldens()
         sys.exit(0)
@@ -1193,6 +1272,7 @@ if __name__ == "__main__":
     wavenet_full_goldens()
     wavenet_onehot_goldens()
     wavenet_onehot_synth_goldens()
+    wavenet_onehot_train_goldens()
     wavenet_deep_goldens()
     av_step_goldens()
     instnorm_goldens()

@@ -22,7 +22,7 @@ class ViaiLibraryError(RuntimeError):
 
 # ABI version THIS file's SIGNATURES / struct mirrors were written against: bumped together with them.  load() compares it with the
 # library, and with the committed header where that is present (a source checkout), so a stale _lib.py cannot call a rebuilt .so.
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 def _header_abi_version():
@@ -157,6 +157,11 @@ SIGNATURES = {
     "viai_wavenet_synth_run": (_I, [C.POINTER(WnSynth), _I, _I, _P]),
     "viai_wn_categorical_ok": (_I, [C.POINTER(WnSynth)]),
     "viai_mulaw_decode": (_I, [_P, _P, _L, _I, _P]),
+    "viai_mulaw_quantize": (_I, [_P, _P, _L, _I, _P]),
+    "viai_masked_ce_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "viai_class_embed_fwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _P]),
+    "viai_class_embed_bwd_segments": (_I, [_L]),
+    "viai_class_embed_bwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _P]),
     "viai_wn_pipe_ok": (_I, [C.POINTER(WnSynth)]),
     "viai_wn_pipe_profile": (_I, [_P, _I]),
     "viai_wn_pipe_image_floats": (C.c_long, [_I]),

@@ -347,6 +347,226 @@ __global__ __launch_bounds__(256) void masked_mean_kernel(const float* __restric
     if (wrow) for (long i = threadIdx.x; i < n; i += 256) wrow[i] = (mask ? mask[i] : 1.f) / (float)sb;
 }
 
+// ---------------------------------------------------------------- masked cross entropy on NHWC rows (loss_functions.py:24-40)
+// One wave per row; lane l holds the float4 column groups 4 l + 256 j (j < NV) of its row, so K = 256 is one 16-byte load per lane.
+constexpr int CE_MAXV = 4;                                            // K <= 1024
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// the row's columns into registers (-inf beyond K), its maximum and sum of exp(x - max): the same instructions in both passes, so the
+// softmax of pass 2 is built from the bits pass 1 saw
+template <int NV>
+__device__ __forceinline__ void ce_row_load(const float* __restrict__ p, int K, int lane, f32x4 (&v)[NV], float& mx, float& se) {
+    mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = 4 * lane + 256 * j;
+        if (c < K) v[j] = *reinterpret_cast<const f32x4*>(p + c);
+        else v[j] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        mx = fmaxf(mx, fmaxf(fmaxf(v[j][0], v[j][1]), fmaxf(v[j][2], v[j][3])));
+    }
+    mx = wave_max(mx);
+    se = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) se += expf(v[j][e] - mx);        // exp(-inf) = 0 in the columns beyond K
+    se = wave_sum(se);
+}
+
+// row (b, t) is scored against target (b, t + shift); tgt < 0 means "no target" (the last `shift` rows of a stream)
+__device__ __forceinline__ void ce_row_target(const int* __restrict__ target, const float* __restrict__ mask, long r, int T, int shift,
+                                              int& tgt, float& m) {
+    const long b = r / T;
+    const int t = (int)(r - b * T);
+    if (t + shift < T) {
+        tgt = target[r + shift];
+        m = mask ? mask[b * (T - shift) + t] : 1.f;
+    } else {
+        tgt = -1;
+        m = 0.f;
+    }
+}
+
+// pass 1: loss[row] = logsumexp(row) - row[target]; meff[row] = the mask as applied (0 on the rows without a target)
+template <int NV>
+__global__ __launch_bounds__(256) void masked_ce_rows_kernel(const float* __restrict__ logits, const int* __restrict__ target,
+                                                             const float* __restrict__ mask, float* __restrict__ loss, float* __restrict__ meff,
+                                                             long rows, int T, int K, int pitch, int shift) {
+    const int lane = threadIdx.x & 63;
+    for (long r = blockIdx.x * 4L + (threadIdx.x >> 6); r < rows; r += gridDim.x * 4L) {
+        int tgt; float m;
+        ce_row_target(target, mask, r, T, shift, tgt, m);
+        f32x4 v[NV];
+        float mx, se;
+        ce_row_load<NV>(logits + r * pitch, K, lane, v, mx, se);
+        float xt = 0.f;                                              // the target's logit less the maximum, picked by column number
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) xt += (4 * lane + 256 * j + e == tgt) ? v[j][e] - mx : 0.f;
+        xt = wave_sum(xt);                                           // one non-zero addend at most: exact
+        if (lane == 0) {
+            const bool in_range = tgt >= 0 && tgt < K;
+            // log(se) - (x_t - max), not (max + log(se)) - x_t: the maximum never meets the small term, so rows of large logits keep its bits
+            loss[r] = in_range ? logf(se) - xt : (m != 0.f ? NAN : 0.f);
+            meff[r] = m;
+        }
+    }
+}
+
+// pass 2: dlogits[row][c] = wrow[row] * (softmax(row)[c] - [c == target]); zeros in the columns K .. pitch and on the rows of weight 0
+template <int NV>
+__global__ __launch_bounds__(256) void masked_ce_grad_kernel(const float* __restrict__ logits, const int* __restrict__ target,
+                                                             const float* __restrict__ wrow, float* __restrict__ dlogits,
+                                                             long rows, int T, int K, int pitch, int shift) {
+    const int lane = threadIdx.x & 63;
+    for (long r = blockIdx.x * 4L + (threadIdx.x >> 6); r < rows; r += gridDim.x * 4L) {
+        const long b = r / T;
+        const int t = (int)(r - b * T);
+        const float w = wrow[r];
+        const int tgt = t + shift < T ? target[r + shift] : -1;
+        float* q = dlogits + r * pitch;
+        const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (w == 0.f) {                                              // wave-uniform
+            for (int c = 4 * lane; c < pitch; c += 256) *reinterpret_cast<f32x4*>(q + c) = zero;
+            continue;
+        }
+        f32x4 v[NV];
+        float mx, se;
+        ce_row_load<NV>(logits + r * pitch, K, lane, v, mx, se);
+        const float lg = logf(se);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = 4 * lane + 256 * j;
+            if (c < K) {
+                f32x4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = w * (expf((v[j][e] - mx) - lg) - (c + e == tgt ? 1.f : 0.f));
+                *reinterpret_cast<f32x4*>(q + c) = o;
+            } else if (c < pitch) {
+                *reinterpret_cast<f32x4*>(q + c) = zero;
+            }
+        }
+        for (int c = 4 * lane + 256 * NV; c < pitch; c += 256) *reinterpret_cast<f32x4*>(q + c) = zero;
+    }
+}
+
+// ---------------------------------------------------------------- first_conv on class indices (wavenet.py:118 on one-hot rows)
+// wt[k][c] = w[c][k]: 32 x 32 tiles through LDS, both sides coalesced
+__global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ w, float* __restrict__ wt, int R, int Cc) {   // w [R][Cc] -> wt [Cc][R]
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
+    for (int i = ty; i < 32; i += 8)
+        if (r0 + i < R && c0 + tx < Cc) tile[i][tx] = w[(size_t)(r0 + i) * Cc + c0 + tx];
+    __syncthreads();
+    for (int i = ty; i < 32; i += 8)
+        if (c0 + i < Cc && r0 + tx < R) wt[(size_t)(c0 + i) * R + r0 + tx] = tile[tx][i];
+}
+
+// h[p][:] = wt[classes[p]][:] + b
+__global__ __launch_bounds__(256) void class_embed_fwd_kernel(const int* __restrict__ classes, const f32x4* __restrict__ wt, const f32x4* __restrict__ b,
+                                                              f32x4* __restrict__ h, long rows, int K, int C4) {
+    const long n = rows * C4;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
+        const long p = i / C4;
+        const int c = (int)(i - p * C4);
+        const int k = classes[p];
+        f32x4 o = f32x4{NAN, NAN, NAN, NAN};
+        if (k >= 0 && k < K) o = wt[(size_t)k * C4 + c] + b[c];
+        h[i] = o;
+    }
+}
+
+// Weight gradient of that layer.  Block (k, s) owns class k in the row segment s: its four waves each scan a quarter of a 2048-row chunk of the
+// class array and list the rows of class k in LDS (ascending inside a wave's quarter, quarters in order), then thread c4 sums the float4 column
+// group c4 of the listed rows of dh in list order, four rows in flight.  part[s][k][:] receives the sum; class_embed_final_kernel adds the
+// segments in order.  Every addition has a fixed place: the same bits on every run, no atomics.  dh is read once in total.
+constexpr int CEB_CHUNK = 2048;
+
+__global__ __launch_bounds__(256) void class_embed_bwd_part_kernel(const float* __restrict__ dh, const int* __restrict__ classes, float* __restrict__ part,
+                                                                   long rows, long seg, int K, int C) {
+    __shared__ int list[4][CEB_CHUNK / 4];
+    __shared__ int cnt[4];
+    const int k = blockIdx.x, s = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int C4 = C / 4;
+    const bool own = (int)threadIdx.x < C4;
+    const long r_end = (s + 1) * seg < rows ? (s + 1) * seg : rows;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (long base = s * seg; base < r_end; base += CEB_CHUNK) {
+        int n = 0;                                                   // wave-uniform
+        const long q0 = base + wave * (CEB_CHUNK / 4);
+        for (int i = 0; i < CEB_CHUNK / 4; i += 64) {
+            const long r = q0 + i + lane;
+            const bool hit = r < r_end && classes[r] == k;
+            const unsigned long long bal = __ballot(hit);
+            if (hit) list[wave][n + __popcll(bal & ((1ull << lane) - 1ull))] = (int)(r - base);
+            n += __popcll(bal);
+        }
+        if (lane == 0) cnt[wave] = n;
+        __syncthreads();
+        if (own) {
+            for (int w = 0; w < 4; ++w) {
+                const int nw = cnt[w];
+                for (int i = 0; i < nw; i += 4) {
+                    f32x4 x[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        if (i + u < nw) x[u] = *reinterpret_cast<const f32x4*>(dh + (size_t)(base + list[w][i + u]) * C + 4 * threadIdx.x);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        if (i + u < nw) acc += x[u];
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (own) *reinterpret_cast<f32x4*>(part + ((size_t)s * K + k) * C + 4 * threadIdx.x) = acc;
+}
+
+// dw[c][k] = sum_s part[s][k][c] (s ascending): 32 x 32 tiles through LDS into the parameter's [C][K] layout
+__global__ __launch_bounds__(256) void class_embed_final_kernel(const float* __restrict__ part, float* __restrict__ dw, int S, int K, int C) {
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int k0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
+    for (int i = ty; i < 32; i += 8) {
+        float a = 0.f;
+        if (k0 + i < K && c0 + tx < C)
+            for (int s = 0; s < S; ++s) a += part[((size_t)s * K + k0 + i) * C + c0 + tx];
+        tile[i][tx] = a;
+    }
+    __syncthreads();
+    for (int i = ty; i < 32; i += 8)
+        if (c0 + i < C && k0 + tx < K) dw[(size_t)(c0 + i) * K + k0 + tx] = tile[tx][i];
+}
+
+// db[c] = sum_k dw[c][k]: one block per channel
+__global__ __launch_bounds__(256) void class_embed_bias_kernel(const float* __restrict__ dw, float* __restrict__ db, int K) {
+    __shared__ float red[4];
+    float a = 0.f;
+    for (int k = threadIdx.x; k < K; k += 256) a += dw[(size_t)blockIdx.x * K + k];
+    a = block_sum(a, red);
+    if (threadIdx.x == 0) db[blockIdx.x] = a;
+}
+
+// waveform -> mu-law class (utils/librivox.py:66-74)
+__global__ __launch_bounds__(256) void mulaw_quantize_kernel(const float* __restrict__ x, int* __restrict__ cls, long n, float mu) {
+    const float l1p = log1pf(mu);
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
+        const float xx = x[i];
+        const float mag = log1pf(mu * fabsf(xx)) / l1p;              // a division: |x| = 1 gives exactly 1, class mu
+        const float y = xx < 0.f ? -mag : mag;
+        const int k = (int)((y + 1.f) * 0.5f * mu);                  // truncation
+        cls[i] = min(max(k, 0), (int)mu);
+    }
+}
+
 __global__ __launch_bounds__(256) void scale_rows_kernel(float* __restrict__ d, const float* __restrict__ gscale, long n) {
     const float g = *gscale;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) d[i] *= g;
@@ -443,6 +663,68 @@ extern "C" int viai_mol_loss(const float* yhat, const float* y, const float* mas
     VIAI_LAUNCH(mol_loss_kernel<10>, dim3(ew_blocks(rows)), dim3(256), 0, st, yhat, y, (const float*)nullptr, loss_rows, (float*)nullptr, rows, pitch, num_classes, log_scale_min);
     VIAI_LAUNCH(masked_mean_kernel, dim3(1), dim3(256), 0, st, loss_rows, mask, rows, loss, wrow);
     if (dyhat) VIAI_LAUNCH(mol_loss_kernel<10>, dim3(ew_blocks(rows)), dim3(256), 0, st, yhat, y, wrow, loss_rows, dyhat, rows, pitch, num_classes, log_scale_min);
+    return viai_launch_status();
+}
+
+template <int NV>
+static void masked_ce_launch(const float* logits, const int* target, const float* mask, float* loss_rows, float* wrow, float* loss,
+                             float* dlogits, long rows, int T, int K, int pitch, int shift, hipStream_t st) {
+    const long nb = (rows + 3) / 4;
+    const int blocks = (int)(nb > 16384 ? 16384 : (nb < 1 ? 1 : nb));
+    float* meff = wrow + rows;
+    // pass 1: per-row losses; masked mean + normalised row weights in a fixed order; pass 2 (if dlogits): gradients with those weights
+    VIAI_LAUNCH(masked_ce_rows_kernel<NV>, dim3(blocks), dim3(256), 0, st, logits, target, mask, loss_rows, meff, rows, T, K, pitch, shift);
+    VIAI_LAUNCH(masked_mean_kernel, dim3(1), dim3(256), 0, st, (const float*)loss_rows, (const float*)meff, rows, loss, wrow);
+    if (dlogits) VIAI_LAUNCH(masked_ce_grad_kernel<NV>, dim3(blocks), dim3(256), 0, st, logits, target, (const float*)wrow, dlogits, rows, T, K, pitch, shift);
+}
+
+extern "C" int viai_masked_ce_loss(const float* logits, const int* target, const float* mask, float* loss_rows, float* wrow, float* loss,
+                                   float* dlogits, int B, int T, int K, int pitch, int shift, void* stream) {
+    if (B < 1 || T < 1 || K < 4 || K % 4 != 0 || pitch < K || pitch % 4 != 0 || K > 256 * CE_MAXV || shift < 0 || shift >= T)
+        return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const long rows = (long)B * T;
+    switch ((K + 255) / 256) {
+        case 1: masked_ce_launch<1>(logits, target, mask, loss_rows, wrow, loss, dlogits, rows, T, K, pitch, shift, st); break;
+        case 2: masked_ce_launch<2>(logits, target, mask, loss_rows, wrow, loss, dlogits, rows, T, K, pitch, shift, st); break;
+        case 3: masked_ce_launch<3>(logits, target, mask, loss_rows, wrow, loss, dlogits, rows, T, K, pitch, shift, st); break;
+        default: masked_ce_launch<4>(logits, target, mask, loss_rows, wrow, loss, dlogits, rows, T, K, pitch, shift, st); break;
+    }
+    return viai_launch_status();
+}
+
+extern "C" int viai_class_embed_fwd(const int* classes, const float* w, const float* b, float* wt, float* h, long rows, int K, int C, void* stream) {
+    if (rows < 1 || K < 1 || C < 4 || C % 4 != 0) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    VIAI_LAUNCH(transpose_kernel, dim3((K + 31) / 32, (C + 31) / 32), dim3(256), 0, st, w, wt, C, K);
+    VIAI_LAUNCH(class_embed_fwd_kernel, dim3(ew_blocks(rows * (C / 4))), dim3(256), 0, st, classes, reinterpret_cast<const f32x4*>(wt),
+                reinterpret_cast<const f32x4*>(b), reinterpret_cast<f32x4*>(h), rows, K, C / 4);
+    return viai_launch_status();
+}
+
+// row segments of the weight gradient: 2048 rows each (one chunk), at most 64 of them
+extern "C" int viai_class_embed_bwd_segments(long rows) {
+    long s = (rows + CEB_CHUNK - 1) / CEB_CHUNK;
+    if (s > 64) s = 64;
+    if (s < 1) s = 1;
+    return (int)s;
+}
+
+extern "C" int viai_class_embed_bwd(const float* dh, const int* classes, float* part, float* dw, float* db, long rows, int K, int C, void* stream) {
+    if (rows < 1 || K < 1 || K > 65535 || C < 4 || C % 4 != 0 || C > 1024) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const int S = viai_class_embed_bwd_segments(rows);
+    long seg = (rows + S - 1) / S;
+    seg = (seg + CEB_CHUNK - 1) / CEB_CHUNK * CEB_CHUNK;               // whole chunks, so a chunk never straddles two segments
+    VIAI_LAUNCH(class_embed_bwd_part_kernel, dim3(K, S), dim3(256), 0, st, dh, classes, part, rows, seg, K, C);
+    VIAI_LAUNCH(class_embed_final_kernel, dim3((C + 31) / 32, (K + 31) / 32), dim3(256), 0, st, (const float*)part, dw, S, K, C);
+    VIAI_LAUNCH(class_embed_bias_kernel, dim3(C), dim3(256), 0, st, (const float*)dw, db, K);
+    return viai_launch_status();
+}
+
+extern "C" int viai_mulaw_quantize(const float* x, int* classes, long n, int mu, void* stream) {
+    if (n < 1 || mu < 1) return (int)hipErrorInvalidValue;
+    VIAI_LAUNCH(mulaw_quantize_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, classes, n, (float)mu);
     return viai_launch_status();
 }
 

@@ -230,6 +230,101 @@ def mol_sample(yhat_nhwc, u1, u2, log_scale_min=-7.0):
     return out
 
 
+def _require_classes(t):
+    if not t.is_cuda:
+        raise _lib.ViaiLibraryError("viai ops run on the GPU only (got a %s tensor); no CPU fallback" % t.device)
+    if t.dtype != torch.int32:
+        raise TypeError("class indices reach the kernels as int32, got %s" % t.dtype)
+
+
+class _MaskedCE(torch.autograd.Function):
+    """MaskedCrossEntropyLoss on NHWC rows: masked mean of the softmax cross-entropy (loss_functions.py:24-40), fused with its gradient."""
+
+    @staticmethod
+    def forward(ctx, yhat, target, mask, K, shift):
+        lib = _lib.load()
+        _require(yhat, mask)
+        _require_classes(target)
+        yhat, target = _c(yhat), _c(target)
+        mask = _c(mask) if mask is not None else None
+        B, T = target.shape
+        pitch = yhat.shape[-1]
+        rows = B * T
+        assert yhat.numel() == rows * pitch, (tuple(yhat.shape), tuple(target.shape))
+        dev = yhat.device
+        loss_rows = torch.empty(rows, device=dev, dtype=torch.float32)
+        wrow = torch.empty(2 * rows, device=dev, dtype=torch.float32)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        dyh = torch.empty_like(yhat) if yhat.requires_grad else None
+        _lib.check(lib.viai_masked_ce_loss(yhat.data_ptr(), target.data_ptr(), _ptr(mask), loss_rows.data_ptr(), wrow.data_ptr(), loss.data_ptr(),
+                                           _ptr(dyh), B, T, K, pitch, shift, _stream()), "viai_masked_ce_loss")
+        ctx.dyh = dyh
+        ctx.mark_non_differentiable(loss_rows)
+        return loss, loss_rows
+
+    @staticmethod
+    def backward(ctx, g, _g2):
+        lib = _lib.load()
+        d = ctx.dyh
+        g = _c(g)
+        _lib.check(lib.viai_scale_by_scalar(d.data_ptr(), g.data_ptr(), d.numel(), _stream()), "viai_scale_by_scalar")
+        return d, None, None, None, None
+
+
+def masked_cross_entropy(yhat_nhwc, target, mask=None, shift=0, num_classes=None):
+    """yhat_nhwc: (B,1,T,P) logit rows, the first K = num_classes (default P) columns are the classes; target: (B,T[,1]) int32 / int64 classes;
+    mask: (B,T[,1]) or (B,T-shift[,1]) floats, entry t weighs logits row t.  shift = s scores row t against target t + s (t < T - s):
+    `criterion(y_hat[:, :, :-1], y[:, 1:])` of the reference's training step is shift = 1 on the unsliced tensors."""
+    B, T = yhat_nhwc.shape[0], yhat_nhwc.shape[-2]
+    K = int(yhat_nhwc.shape[-1] if num_classes is None else num_classes)
+    shift = int(shift)
+    target = target.reshape(B, T).to(torch.int32)
+    if mask is not None:
+        mask = mask.reshape(B, -1).float()
+        if mask.shape[1] > T - shift:
+            mask = mask[:, :T - shift]
+        elif mask.shape[1] < T - shift:                                               # sequence_mask without max_len: the missing tail is 0
+            mask = torch.nn.functional.pad(mask, (0, T - shift - mask.shape[1]))
+        mask = mask.contiguous()
+    loss, _ = _MaskedCE.apply(yhat_nhwc, target, mask, K, shift)
+    return loss
+
+
+class _ClassEmbed(torch.autograd.Function):
+    """first_conv of the one-hot network on class indices: h[p][:] = w[:, class[p]] + b -- Conv1d1x1(K, C) applied to one-hot rows
+    (wavenet.py:118 on the input of data_loader_utils.py:278-281), without the rows."""
+
+    @staticmethod
+    def forward(ctx, classes, w, b):
+        lib = _lib.load()
+        _require(w, b)
+        _require_classes(classes)
+        classes, w, b = _c(classes), _c(w), _c(b)
+        Cc, K = w.shape
+        B, T = classes.shape
+        wt = torch.empty((K, Cc), device=w.device, dtype=torch.float32)
+        h = torch.empty((B, 1, T, Cc), device=w.device, dtype=torch.float32)
+        _lib.check(lib.viai_class_embed_fwd(classes.data_ptr(), w.data_ptr(), b.data_ptr(), wt.data_ptr(), h.data_ptr(), B * T, K, Cc, _stream()),
+                   "viai_class_embed_fwd")
+        ctx.save_for_backward(classes)
+        ctx.shape = (Cc, K)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        lib = _lib.load()
+        (classes,) = ctx.saved_tensors
+        dh = _c(dh)
+        Cc, K = ctx.shape
+        rows = classes.numel()
+        part = torch.empty(K * Cc * lib.viai_class_embed_bwd_segments(rows), device=dh.device, dtype=torch.float32)
+        dw = torch.empty((Cc, K), device=dh.device, dtype=torch.float32)
+        db = torch.empty(Cc, device=dh.device, dtype=torch.float32)
+        _lib.check(lib.viai_class_embed_bwd(dh.data_ptr(), classes.data_ptr(), part.data_ptr(), dw.data_ptr(), db.data_ptr(), rows, K, Cc, _stream()),
+                   "viai_class_embed_bwd")
+        return None, dw, db
+
+
 def receptive_field_size(total_layers, num_cycles, kernel_size, dilation=lambda x: 2 ** x):
     """samples of context one output sees: (k - 1) * sum of the layer dilations + 1 (wavenet_vocoder/wavenet.py:41-59; 505 for the
     reference's 24 layers / 4 cycles / k = 3).  `dilation(i)` maps the position inside a cycle to the dilation."""
@@ -263,6 +358,18 @@ def mulaw_decode(classes, mu=255):
     _lib.check(lib.viai_mulaw_decode(k.data_ptr(), out.data_ptr(), k.numel(), int(mu), torch.cuda.current_stream().cuda_stream),
                "viai_mulaw_decode")
     return out
+
+
+def mulaw_quantize(x, mu=255):
+    """waveform in [-1, 1] (float tensor, any shape, on the GPU) -> mu-law classes (int64, like the targets the reference's loader builds):
+    y = sign(x) log1p(mu |x|) / log1p(mu), class = trunc((y + 1) / 2 * mu) clamped to [0, mu] -- the closed form of the `P.mulaw_quantize`
+    of the reference's data preparation (utils/librivox.py:66-74).  HIP kernel `viai_mulaw_quantize`."""
+    lib = _lib.load()
+    xx = x.to(torch.float32).contiguous()
+    out = torch.empty(xx.shape, dtype=torch.int32, device=xx.device)
+    _lib.check(lib.viai_mulaw_quantize(xx.data_ptr(), out.data_ptr(), xx.numel(), int(mu), torch.cuda.current_stream().cuda_stream),
+               "viai_mulaw_quantize")
+    return out.long()
 
 
 # ----------------------------------------------------------------------------- modules
@@ -431,8 +538,14 @@ class WaveNet(nn.Module):
         return g.expand(B, -1, T).transpose(1, 2).unsqueeze(1).contiguous()          # (B,1,T,gin)
 
     def forward_nhwc(self, x, c=None, g=None):
-        """x (B,1,T) or (B,out,T); returns (B,1,T,P) with P = out_channels padded to a multiple of 4."""
-        B, _, T = x.size()
+        """x (B,1,T), (B,out,T) or, for the one-hot network, integer classes (B,T); returns (B,1,T,P) with P = out_channels padded to a
+        multiple of 4."""
+        classes = None
+        if not self.scalar_input and x.dim() == 2 and not torch.is_floating_point(x):
+            classes = x.to(torch.int32)                                               # class form of the first layer: no one-hot tensor
+            B, T = classes.shape
+        else:
+            B, _, T = x.size()
         g_n = self._global(g, B, T)
         c = self._upsample(c)
         c_n = None
@@ -441,6 +554,8 @@ class WaveNet(nn.Module):
             c_n = c.transpose(1, 2).unsqueeze(1).contiguous()                         # (B,1,T,cin)
         if self.scalar_input:
             h = _Outer.apply(x.reshape(B, 1, T).contiguous(), normed_weight(self.first_conv).reshape(-1), self.first_conv.bias)
+        elif classes is not None:
+            h = _ClassEmbed.apply(classes, normed_weight(self.first_conv).reshape(self.first_conv.out_channels, -1), self.first_conv.bias)
         else:
             h = conv1d_apply(x.transpose(1, 2).unsqueeze(1).contiguous(), self.first_conv)
         skips = None
@@ -726,3 +841,30 @@ class DiscretizedMixturelogisticLoss(nn.Module):
         else:
             yh = input
         return mol_loss(yh, target, mask, self.quantize_channels, self.log_scale_min)
+
+
+class MaskedCrossEntropyLoss(nn.Module):
+    """loss_functions.py:24-40.  input: (B, K, T), (B, K, T, 1) (what the reference's criterion receives, train.py's __train_step) or the NHWC
+    tensor (B, 1, T, P) of WaveNet.forward_nhwc (its first `num_classes` columns, all P by default); target (B, T, 1) or (B, T), int32 or int64.
+    `shift = s` scores input step t against target step t + s: criterion(y_hat, y, lengths=..., max_len=T - 1, shift=1) is the reference's
+    criterion(y_hat[:, :, :-1], y[:, 1:], lengths=..., max_len=T - 1) without the sliced copies."""
+
+    def __init__(self, num_classes=None):
+        super().__init__()
+        self.num_classes = num_classes
+
+    def forward(self, input, target, lengths=None, mask=None, max_len=None, shift=0):
+        if lengths is None and mask is None:
+            raise RuntimeError("Should provide either lengths or mask")
+        if mask is None:
+            mask = sequence_mask(lengths, max_len).unsqueeze(-1)
+        K = self.num_classes
+        if input.dim() == 4 and input.size(1) == 1:                                   # NHWC rows
+            yh = input
+        else:                                                                         # (B, K, T[, 1]) -> NHWC rows, padded to whole float4s
+            if input.dim() == 4:
+                input = input.squeeze(-1)
+            B, Kc, T = input.shape
+            K = Kc if K is None else K
+            yh = torch.nn.functional.pad(input.transpose(1, 2), (0, (-Kc) % 4)).reshape(B, 1, T, -1).contiguous()
+        return masked_cross_entropy(yh, target, mask.to(yh.device), shift, K)
