@@ -293,6 +293,14 @@ int viai_glu_bwd(const float* dz, const float* y, const float* yc, float* dy, lo
 /* out = (a + b) * s (b may be NULL): residual / skip scaling by sqrt(0.5) (modules.py:209, wavenet.py:222-226) */
 int viai_add_scale(const float* a, const float* b, float* out, float s, long n, void* stream);
 int viai_relu_fwd(const float* a, float* out, long n, void* stream);
+/* Dropout of the residual layers (modules.py:173-175) with a counter-based mask (csrc/dropout.hip; added under ABI 20, a purely additive
+ * symbol): y[i] = keep(i) ? x[i] * scale : +0.0f, scale = (float)(1 / (1 - p)) computed in double and rounded once; a dropped element is a
+ * select, +0 whatever x[i] holds.  keep(i) is a function of (seed, offset, i) alone: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key
+ * increments 0x9E3779B9 / 0xBB67AE85) with counter (j lo, j hi, offset lo, offset hi), key (seed lo, seed hi) gives the four words of elements
+ * 4 j .. 4 j + 3; element 4 j + k is kept iff word k >= (uint32_t) floor(p * 2^32).  The backward pass is the same call on dy with the same
+ * (p, seed, offset): no mask is stored.  x and y may be the same pointer; both 16-byte aligned when n >= 4.  Returns 1 (invalid value) on the
+ * host, before any launch, for p < 0, p >= 1, NaN p, n < 0 or a misaligned pointer; n == 0 returns 0 without a launch.                  */
+int viai_dropout(const float* x, float* y, long n, double p, unsigned long long seed, unsigned long long offset, void* stream);
 /* first_conv for scalar input, Conv1d1x1(1, C): y[p][c] = x[p]*w[c] + b[c] (wavenet.py:118) and its weight grads */
 int viai_outer_fwd(const float* x, const float* w, const float* b, float* y, long rows, int C, void* stream);
 int viai_outer_bwd_blocks(long rows);

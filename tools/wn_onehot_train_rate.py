@@ -9,7 +9,11 @@ Timed: forward + backward of the input layer plus the loss (the upstream gradien
 whole teacher-forced forward + backward of the 24-layer network, so the share of the two ends is visible.  The byte model of the two ends
 is recorded next to the times.  The file's `parity` key belongs to tests/test_wavenet_onehot_train_gpu.py and is kept.
 
-    python tools/wn_onehot_train_rate.py [--out profiles/wn_onehot_train.json] [--reps 20] [--whole-reps 20]
+    python tools/wn_onehot_train_rate.py [--out profiles/wn_onehot_train.json] [--reps 20] [--whole-reps 20] [--dropout P]
+
+--dropout P (default 0: the figures above) builds the network with the residual layers' dropout on (the reference trains with 0.05) under a fixed
+seed; the figures of such a run, with the peak of torch.cuda.max_memory_allocated() over one class-form step, go under the file's `dropout` key
+and leave the others as they are.
 """
 import argparse
 import json
@@ -53,13 +57,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--length", type=int, default=4096)
+    ap.add_argument("--dropout", type=float, default=0.0)
     args = ap.parse_args()
     assert args.reps >= 20 and args.whole_reps >= 20, "the median is over at least 20 repetitions"
     B, T, K, Cc = args.batch, args.length, 256, 512
     rows = B * T
     torch.manual_seed(0)
-    net = wn.WaveNet(out_channels=K, layers=24, stacks=4, residual_channels=Cc, gate_channels=512, skip_out_channels=256, dropout=0.0,
+    net = wn.WaveNet(out_channels=K, layers=24, stacks=4, residual_channels=Cc, gate_channels=512, skip_out_channels=256, dropout=args.dropout,
                      cin_channels=80, upsample_scales=[4, 4, 4, 4], scalar_input=False).cuda().train()
+    if args.dropout > 0:
+        net.seed_dropout(0)
     first = net.first_conv
     idx = torch.randint(0, K, (B, T), device="cuda")
     c = torch.rand(B, 80, T // 256, device="cuda")
@@ -105,8 +112,16 @@ def main():
     ends, ends_range = alternate({"dense": ends_dense, "class": ends_class}, args.warmup, args.reps)
     whole, whole_range = alternate({"dense": whole_dense, "class": whole_class}, 2, args.whole_reps)
     segs = wn._lib.load().viai_class_embed_bwd_segments(rows)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    whole_class()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated()
     doc = json.load(open(args.out)) if os.path.exists(args.out) else {}
-    doc.update({
+    res = doc if args.dropout == 0 else doc.setdefault("dropout", {})
+    if args.dropout > 0:
+        res.update({"p": args.dropout, "whole_step_class_peak_bytes": peak})
+    res.update({
         "shape": {"B": B, "T": T, "K": K, "C": Cc, "rows": rows, "layers": 24},
         "method": "HIP events around forward + backward, %d warm-up, median of %d (ends) / %d (whole step) repetitions, the two paths alternating "
                   "inside every repetition, one process" % (args.warmup, args.reps, args.whole_reps),
@@ -128,7 +143,8 @@ def main():
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1, sort_keys=True)
         f.write("\n")
-    print(json.dumps({k: doc[k] for k in ("ends_ms", "ends_ratio_class_over_dense", "whole_step_ms", "whole_step_ratio_class_over_dense")}))
+    shown = {k: res[k] for k in ("ends_ms", "ends_ratio_class_over_dense", "whole_step_ms", "whole_step_ratio_class_over_dense")}
+    print(json.dumps(dict(shown, dropout=args.dropout, whole_step_class_peak_bytes=peak)))
 
 
 if __name__ == "__main__":

@@ -144,6 +144,7 @@ SIGNATURES = {
     "viai_glu_bwd": (_I, [_P, _P, _P, _P, _L, _I, _P]),
     "viai_add_scale": (_I, [_P, _P, _P, _F, _L, _P]),
     "viai_relu_fwd": (_I, [_P, _P, _L, _P]),
+    "viai_dropout": (_I, [_P, _P, _L, _D, C.c_ulonglong, C.c_ulonglong, _P]),
     "viai_outer_fwd": (_I, [_P, _P, _P, _P, _L, _I, _P]),
     "viai_outer_bwd_blocks": (_I, [_L]),
     "viai_outer_bwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _P]),

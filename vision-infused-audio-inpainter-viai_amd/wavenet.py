@@ -103,6 +103,60 @@ def add_scale(a, b, s):
     return _AddScale.apply(a, b, float(s))
 
 
+_U64 = (1 << 64) - 1
+
+
+def _dropout_launch(x, p, seed, offset, out=None):
+    lib = _lib.load()
+    _require(x)
+    x = _c(x)
+    if x.data_ptr() % 16:
+        x = x.clone()                                                                 # a view that starts inside a float4: an aligned copy
+    y = torch.empty_like(x) if out is None else out
+    _lib.check(lib.viai_dropout(x.data_ptr(), y.data_ptr(), x.numel(), p, seed, offset, _stream()), "viai_dropout")
+    return y
+
+
+class _Dropout(torch.autograd.Function):
+    """y = x * keep / (1 - p), keep a function of (seed, offset, element index) alone (csrc/dropout.hip): the backward pass runs the same
+    kernel on the incoming gradient with the three numbers kept on ctx; no tensor is saved."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, offset):
+        ctx.p, ctx.seed, ctx.offset = p, seed, offset
+        return _dropout_launch(x, p, seed, offset)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _dropout_launch(g, ctx.p, ctx.seed, ctx.offset), None, None, None
+
+
+def _dropout_args(p, seed, offset):
+    p = float(p)
+    if not 0.0 <= p < 1.0:                                                            # NaN fails both comparisons
+        raise ValueError("dropout: p must be in [0, 1), got %r" % (p,))
+    return p, int(seed) & _U64, int(offset) & _U64
+
+
+def dropout(x, p, seed, offset):
+    """Training-mode dropout (F.dropout with training=True) with a reproducible mask: element i of the flattened tensor is kept iff word i % 4 of
+    Philox4x32-10(counter = (i // 4, offset), key = seed) is >= floor(p * 2^32); kept values are x * float32(1 / (1 - p)), dropped ones +0.
+    seed, offset: integers taken modulo 2^64.  p == 0 returns x itself, without a launch."""
+    p, seed, offset = _dropout_args(p, seed, offset)
+    if p == 0.0:
+        return x
+    return _Dropout.apply(x, p, seed, offset)
+
+
+def dropout_mask(shape, p, seed, offset, device="cuda"):
+    """the bool keep-mask `dropout` applies to a tensor of this shape with the same (p, seed, offset): the kernel run on ones"""
+    p, seed, offset = _dropout_args(p, seed, offset)
+    ones = torch.ones(shape, device=device, dtype=torch.float32)
+    if p == 0.0:
+        return ones.bool()
+    return _dropout_launch(ones, p, seed, offset, out=ones) != 0
+
+
 class _Relu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a):
@@ -453,6 +507,9 @@ class ResidualConv1dGLU(nn.Module):
                  dropout=1 - 0.95, padding=None, dilation=1, causal=True, bias=True, weight_normalization=True):
         super().__init__()
         self.dropout = dropout
+        # the dropout stream of this layer (plain attributes, not buffers: state_dict() is the reference's): training forward number n
+        # uses the mask of (seed, offset = n * 1024 + layer_index)
+        self.layer_index, self._drop_seed, self._drop_calls = 0, None, 0
         skip_out_channels = residual_channels if skip_out_channels is None else skip_out_channels
         if padding is None:
             padding = (kernel_size - 1) * dilation if causal else (kernel_size - 1) // 2 * dilation
@@ -466,8 +523,12 @@ class ResidualConv1dGLU(nn.Module):
 
     def forward_nhwc(self, x, c=None, g=None):
         residual = x
-        if self.training and self.dropout > 0:
-            x = torch.nn.functional.dropout(x, p=self.dropout, training=True)   # RNG-dependent: parity tests use dropout = 0
+        if self.training and self.dropout > 0:                                  # modules.py:173-175: the residual keeps the un-dropped input
+            assert 0 <= self.layer_index < 1024, "dropout offsets are calls * 1024 + layer_index"
+            if self._drop_seed is None:                                         # never seeded: one draw from torch's default CPU generator
+                self._drop_seed = int(torch.empty((), dtype=torch.int64).random_())
+            x = dropout(x, self.dropout, self._drop_seed, self._drop_calls * 1024 + self.layer_index)
+            self._drop_calls += 1
         y = conv1d_apply(x, self.conv, causal_crop=self.causal)                 # (B,1,T,gate)  modules.py:176-181
         yc = None
         if c is not None:
@@ -496,6 +557,8 @@ class WaveNet(nn.Module):
         self.conv_layers = nn.ModuleList([
             ResidualConv1dGLU(residual_channels, gate_channels, kernel_size, skip_out_channels, cin_channels, gin_channels, dropout,
                               dilation=2 ** (i % per), bias=True, weight_normalization=weight_normalization) for i in range(layers)])
+        for i, f in enumerate(self.conv_layers):
+            f.layer_index = i                                          # the layers of one training forward draw different dropout masks
         self.last_conv_layers = nn.ModuleList([nn.ReLU(inplace=True), Conv1d1x1(skip_out_channels, skip_out_channels, True, weight_normalization),
                                                nn.ReLU(inplace=True), Conv1d1x1(skip_out_channels, out_channels, True, weight_normalization)])
         self.embed_speakers = None
@@ -512,6 +575,27 @@ class WaveNet(nn.Module):
                 self.upsample_conv.append(_wn(m, weight_normalization))
                 self.upsample_conv.append(nn.ReLU(inplace=True))
         self.receptive_field = (kernel_size - 1) * sum(2 ** (i % per) for i in range(layers)) + 1
+
+    def seed_dropout(self, seed, calls=0):
+        """Fix the dropout masks of training: forward number n (counted from `calls`) of layer l drops by (seed, offset = n * 1024 + l).
+        Without it every layer draws its seed from torch's default CPU generator at its first training forward."""
+        for f in self.conv_layers:
+            f._drop_seed, f._drop_calls = int(seed) & _U64, int(calls)
+
+    def dropout_state(self):
+        """{"seed", "calls"}: what load_dropout_state needs to continue the same mask sequence (kept beside a checkpoint; not in state_dict()).
+        "seed" is one integer after seed_dropout, None before the first training forward, the per-layer list where the layers drew their own."""
+        seeds = [f._drop_seed for f in self.conv_layers]
+        return {"seed": seeds[0] if all(v == seeds[0] for v in seeds) else seeds, "calls": [f._drop_calls for f in self.conv_layers]}
+
+    def load_dropout_state(self, d):
+        seeds, calls = d["seed"], list(d["calls"])
+        if not isinstance(seeds, (list, tuple)):
+            seeds = [seeds] * len(self.conv_layers)
+        if not len(seeds) == len(calls) == len(self.conv_layers):
+            raise ValueError("load_dropout_state: the state is for %d layers, the network has %d" % (len(calls), len(self.conv_layers)))
+        for f, sd, n in zip(self.conv_layers, seeds, calls):
+            f._drop_seed, f._drop_calls = (None if sd is None else int(sd) & _U64), int(n)
 
     def has_speaker_embedding(self):
         return self.embed_speakers is not None
