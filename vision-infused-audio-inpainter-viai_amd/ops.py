@@ -11,6 +11,7 @@ There is no CPU path: a non-CUDA tensor or a missing library raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -52,13 +53,25 @@ def is_p16(t):
     return t is not None and getattr(t, "_viai_p16", False)
 
 
+Caps = collections.namedtuple("Caps", "fwd_f16 dgrad_f16 wgrad_f16 cin1_bn p16")
+
+
+def _caps(d):
+    """what the library's kernels do for the layer of descriptor d: f16x2 forward / data gradient / weight gradient, the fused Cin = 1 layer, and
+    the mask of operands that may arrive pre-split (P16_OK_*).  Asked once and kept in the descriptor.
+    (the library reads VIAI_WGRAD_PATCH_S2 per call -- tests flip it at run time -- and both the weight-gradient answer and the mask depend on it, so the
+    record is keyed on its value)"""
+    key = ("caps", os.environ.get("VIAI_WGRAD_PATCH_S2"))
+    c = d.get(key)
+    if c is None:
+        lib, ref = _lib.load(), d["ref"]
+        c = d[key] = Caps(bool(lib.viai_conv2d_fwd_f16_ok(ref)), bool(lib.viai_conv2d_dgrad_f16_ok(ref)), bool(lib.viai_conv2d_wgrad_f16_ok(ref)),
+                          bool(lib.viai_conv2d_cin1_bn_ok(ref)), int(lib.viai_conv2d_p16_ok(ref)))
+    return c
+
+
 def p16_mask(d):
-    # (the library reads two of its kernel-family switches per call -- tests flip them at run time -- so the cached mask is keyed on them)
-    key = ("p16", os.environ.get("VIAI_WGRAD_PATCH_S2"))
-    m = d.get(key)
-    if m is None:
-        m = d[key] = int(_lib.load().viai_conv2d_p16_ok(d["ref"]))
-    return m
+    return _caps(d).p16
 
 
 def _p16_decode(t, amax):
@@ -96,9 +109,8 @@ def conv_wgrad_takes_p16(x_shape, weight, kernel, stride, padding, transposed):
     if C1 % 32 != 0:
         return False
     d = conv_desc(N, IH, IW, C1, 0, Cout, kernel[0], kernel[1], stride[0], stride[1], padding[0], padding[1], 1 if transposed else 0)
-    if d.get("wgrad_f16") is None:
-        d["wgrad_f16"] = bool(_lib.load().viai_conv2d_wgrad_f16_ok(d["ref"]))
-    return bool(p16_mask(d) & P16_OK_WGRAD_X) and d["wgrad_f16"]
+    caps = _caps(d)
+    return bool(caps.p16 & P16_OK_WGRAD_X) and caps.wgrad_f16
 
 
 # Gradient-ready hooks (set by model.AudioModel for the data-parallel exchange): {weight.data_ptr(): callable}.  The callable runs
@@ -162,6 +174,12 @@ def _stream():
 
 def _ptr(t):
     return 0 if t is None else t.data_ptr()
+
+
+def _rows(coef):
+    """pointers to the four rows (mean, invstd, scale, shift) of a layer's (4, C) BatchNorm coefficient tensor"""
+    p, step = coef.data_ptr(), 4 * coef.stride(0)
+    return p, p + step, p + 2 * step, p + 3 * step
 
 
 def _require(*tensors):
@@ -431,8 +449,7 @@ def _bn_finalize(lib, d, stat, M, Cc, gamma, beta, rmean, rvar, nbt, cfg, coef, 
     kernel's tiles are clipped at the map's edge (viai_conv2d_stat_tiles); `lin`: the pre-split forward ran on the linear-tile kernel, whose
     partial blocks are 128 consecutive pixels (VIAI_P16_OK_FWD_LIN)"""
     th, tw = (0, 0) if lin else d["tiles"]
-    tail = (Cc, gamma.data_ptr(), beta.data_ptr(), _ptr(rmean), _ptr(rvar), _ptr(nbt), cfg["momentum"], cfg["eps"],
-            coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), st)
+    tail = (Cc, gamma.data_ptr(), beta.data_ptr(), _ptr(rmean), _ptr(rvar), _ptr(nbt), cfg["momentum"], cfg["eps"], *_rows(coef), st)
     if lin:
         # (the kernel's partials are per 128 pixels or merged per persistent block: the library applies the launch's rule, round 6)
         _lib.check(lib.viai_bn_finalize_lin(stat.data_ptr(), M, *tail), "viai_bn_finalize_lin")
@@ -465,11 +482,44 @@ def conv_desc(N, IH, IW, C1, C2, Cout, kh, kw, sh, sw, ph, pw, transposed, dh=1,
     return d
 
 
+def _wgrad_side(trail, st):
+    """where a weight-gradient launch goes: (stream object for _scratch, raw handle).  With `trail` and a WGRAD_STREAM, the side stream,
+    ordered behind what the current stream has queued so far -- the caller then keeps the launch's operands alive in _deferred; otherwise (None, st).
+    (no `with torch.cuda.stream(...)`: the launch takes the stream handle explicitly, and entering / leaving the context costs ~25 us of
+    host time per layer)"""
+    if not trail or WGRAD_STREAM is None:
+        return None, st
+    ev = torch.cuda.Event()
+    ev.record()
+    WGRAD_STREAM.wait_event(ev)
+    return WGRAD_STREAM, WGRAD_STREAM.cuda_stream
+
+
+def _grad_ready(weight):
+    """the layer owning `weight` has queued its last gradient launch: fire its GRAD_HOOKS entry"""
+    if GRAD_HOOKS:
+        hook = GRAD_HOOKS.get(weight.data_ptr())
+        if hook is not None:
+            hook()
+
+
+def _bn_targets(gt, need_g, need_be, training, Cc, dev):
+    """where a BatchNorm backward writes its gamma / beta gradients, and its flag word (1: batch statistics, 2: accumulate):
+    (pg, pb, dgamma, dbeta, flags).  In place into the arena views of gt where both exist and both are wanted -- autograd then gets None --
+    into fresh tensors otherwise."""
+    flags = 1 if training else 0
+    if gt[2] is not None and gt[3] is not None and need_g and need_be:
+        return gt[2], gt[3], None, None, flags | 2
+    dgamma = torch.empty(Cc, device=dev, dtype=torch.float32) if need_g else None
+    dbeta = torch.empty(Cc, device=dev, dtype=torch.float32) if need_be else None
+    return dgamma, dbeta, dgamma, dbeta, flags
+
+
 def _wgrad_call(lib, d, x, x2, dy, ws, dw, db, acc, amax, xa, flags, handle):
     if flags:
         _lib.check(lib.viai_conv2d_wgrad_f16_p16(d["ref"], x.data_ptr(), _ptr(x2), dy.data_ptr(), ws.data_ptr(), dw.data_ptr(), db, acc,
                                                  amax.data_ptr(), _ptr(xa), flags, handle), "viai_conv2d_wgrad_f16_p16")
-    elif amax is not None and d["wgrad_f16"]:
+    elif amax is not None and _caps(d).wgrad_f16:
         _lib.check(lib.viai_conv2d_wgrad_f16(d["ref"], x.data_ptr(), _ptr(x2), dy.data_ptr(), ws.data_ptr(), dw.data_ptr(), db, acc,
                                              amax.data_ptr(), _ptr(xa), handle), "viai_conv2d_wgrad_f16")
     else:
@@ -486,7 +536,8 @@ def _conv_grads(lib, d, cfg, dims, has_bn, has_bias, needs, xa, x, x2, weight, d
     need_x, need_x2, need_w, need_b = needs
     gt = cfg.get("gt") or (None, None, None, None)
     dw = db = dx = dx2 = None
-    if need_w and x_p16 and not (p16_mask(d) & P16_OK_WGRAD_X and (amax is not None and d.get("wgrad_f16"))):
+    caps = _caps(d)
+    if need_w and x_p16 and not (caps.p16 & P16_OK_WGRAD_X and (amax is not None and caps.wgrad_f16)):
         x = _p16_decode(x, xa)                 # (a layer whose weight gradient cannot stage pieces: not reached by the networks of this package)
         x_p16 = False
     # dy_w: dy once more as planes, for the weight gradient only (the data gradient below reads the fp32 `dy`)
@@ -506,19 +557,13 @@ def _conv_grads(lib, d, cfg, dims, has_bn, has_bias, needs, xa, x, x2, weight, d
             else:
                 db = torch.empty(Cout, device=dev, dtype=torch.float32)
         want_db = db is not None and not shadowed
-        if WGRAD_STREAM is not None and acc_w and (acc_b or not want_db):
+        if acc_w == acc_b or not want_db:
             # in-place accumulation into the arenas: nothing flows back through autograd, so the launch can trail
-            ev = torch.cuda.Event()
-            ev.record()
-            WGRAD_STREAM.wait_event(ev)
-            # (no `with torch.cuda.stream(...)` here: the launch takes the stream handle explicitly, and entering / leaving the
-            # context costs ~25 us of host time per layer)
-            ws = _scratch("wgrad", d["ws_floats"], dev, WGRAD_STREAM)
-            _wgrad_call(lib, d, x, x2, dyw, ws, dw, db.data_ptr() if want_db else 0, 1, amax, xa, flags, WGRAD_STREAM.cuda_stream)
-            _deferred.append((x, x2, dyw, weight, amax, xa))
-        elif acc_w == acc_b or not want_db:
-            ws = _scratch("wgrad", d["ws_floats"], dev)
-            _wgrad_call(lib, d, x, x2, dyw, ws, dw, db.data_ptr() if want_db else 0, 1 if acc_w else 0, amax, xa, flags, st)
+            side, handle = _wgrad_side(acc_w and (acc_b or not want_db), st)
+            ws = _scratch("wgrad", d["ws_floats"], dev, side)
+            _wgrad_call(lib, d, x, x2, dyw, ws, dw, db.data_ptr() if want_db else 0, 1 if acc_w else 0, amax, xa, flags, handle)
+            if side is not None:
+                _deferred.append((x, x2, dyw, weight, amax, xa))
         else:   # mixed modes (only outside AudioModel): two calls keep the accumulate flag consistent
             if flags:
                 raise RuntimeError("pre-split operands with a mixed accumulate / overwrite bias gradient")
@@ -532,10 +577,7 @@ def _conv_grads(lib, d, cfg, dims, has_bn, has_bias, needs, xa, x, x2, weight, d
             dw = None
         if acc_b:
             db = None
-        if GRAD_HOOKS:
-            hook = GRAD_HOOKS.get(weight.data_ptr())
-            if hook is not None:
-                hook()
+        _grad_ready(weight)
     if need_x or need_x2:
         dx = torch.empty((N, IH, IW, C1), device=dev, dtype=torch.float32)
         dx2 = torch.empty((N, IH, IW, C2), device=dev, dtype=torch.float32) if C2 > 0 else None
@@ -543,7 +585,7 @@ def _conv_grads(lib, d, cfg, dims, has_bn, has_bias, needs, xa, x, x2, weight, d
             wp = _packed(weight, d, 2, st)
             _lib.check(lib.viai_conv2d_dgrad_f16_p16(d["ref"], dy.data_ptr(), wp.data_ptr(), dx.data_ptr(), _ptr(dx2), amax.data_ptr(), st),
                        "viai_conv2d_dgrad_f16_p16")
-        elif amax is not None and d["dgrad_f16"]:
+        elif amax is not None and caps.dgrad_f16:
             wp = _packed(weight, d, 2, st)
             _lib.check(lib.viai_conv2d_dgrad_f16(d["ref"], dy.data_ptr(), wp.data_ptr(), dx.data_ptr(), _ptr(dx2), amax.data_ptr(), st),
                        "viai_conv2d_dgrad_f16")
@@ -552,6 +594,156 @@ def _conv_grads(lib, d, cfg, dims, has_bn, has_bias, needs, xa, x, x2, weight, d
             _lib.check(lib.viai_conv2d_dgrad(d["ref"], dy.data_ptr(), wp.data_ptr(), dx.data_ptr(), _ptr(dx2), st),
                        "viai_conv2d_dgrad")
     return dx, dx2, dw, db
+
+
+# ------------------------------------------------------------------------------------------------------ the fused layer
+# Form in which a layer's dy (the gradient of the conv's output) leaves its BatchNorm backward:
+#   DY_PLAIN   fp32                                                   viai_bn_act_bwd_amax
+#   DY_PLANES  pre-split (P16): every kernel that reads it stages pieces   viai_bn_act_bwd_p16
+#   DY_TWIN    both, in one apply pass: only the weight gradient stages pieces, the data gradient reads fp32   viai_bn_act_bwd_p16_twin
+#   DY_JOIN    planes, and the residual join's masked gradient sum is made inside the reduce pass   viai_bn_join_bwd_p16
+#   DY_POOL    fp32, gathered from the pooled gradient and the argmax bytes   viai_bn_act_pool_bwd_amax2
+DY_PLAIN, DY_PLANES, DY_TWIN, DY_JOIN, DY_POOL = range(5)
+
+
+def _dy_form(caps, need_x, need_w, need_b, act, tail, has_bias, training, Cout, p16, f16_backward, join_fused):
+    """(want_amax, form) for the BatchNorm backward of one fused layer.  Pure: no tensors, no library.
+    want_amax: the apply pass reduces max |dy|, the operand scale of the f16x2 data- and weight-gradient kernels.
+    dy goes out as planes when every kernel that reads it stages pieces -- this layer's data gradient (if needed) and weight gradient (if
+    needed); a bias gradient behind an eval-mode BatchNorm (column sums of dy) needs the fp32 tensor.  `need_x` is what the caller counts as
+    a data gradient: _ConvBnAct passes need_x alone, the Cout = 1 pair need_x or need_x2 (and takes DY_PLANES or nothing)."""
+    f16d, f16w, pm = caps.dgrad_f16, caps.wgrad_f16, caps.p16
+    want_amax = bool(f16_backward and ((f16d and need_x) or (f16w and need_w)))
+    if tail == "pool":
+        return want_amax, DY_POOL
+    # (behind a residual join the activation's gradient is taken in front of the BatchNorm backward: the apply pass sees none)
+    if not (p16 and want_amax and Cout % 32 == 0 and (act != ACT_SIGMOID or tail == "res") and not (need_b and has_bias and not training)):
+        return want_amax, DY_PLAIN
+    w_planes = f16w and bool(pm & P16_OK_WGRAD_DY)
+    if (not need_x or (f16d and pm & P16_OK_DGRAD_DY)) and (not need_w or w_planes):
+        return want_amax, DY_JOIN if (tail == "res" and act == ACT_RELU and join_fused) else DY_PLANES
+    return want_amax, DY_TWIN if (need_x and need_w and w_planes) else DY_PLAIN
+
+
+def _stage_input(d, caps, x, x2, xp, cfg, st):
+    """the conv's input as its forward kernel takes it: (x, x is pre-split, operand magnitude or None).  A pre-split x the layer has no loader
+    for is decoded (the networks of this package ask conv_takes_p16 first); the planes carry the scale they were written with; an fp32 input
+    of an f16x2 kernel gets its magnitude from the tensors' provenance or one absmax pass."""
+    if xp and (x2 is not None or (caps.p16 & P16_OK_FWD_X) == 0):
+        x, xp = p16_decode(x), False
+    if xp:
+        return x, True, amax_of(x)
+    return x, False, (_input_amax(x, x2, cfg.get("xa_in", (None, None)), st) if (caps.fwd_f16 and F16_DYNAMIC) else None)
+
+
+def _conv_fwd(lib, d, x, x2, xp, xa, wp, bias, out, stat, act, st):
+    if xp:
+        _lib.check(lib.viai_conv2d_fwd_p16(d["ref"], x.data_ptr(), wp.data_ptr(), _ptr(bias), out.data_ptr(), stat, act, xa.data_ptr(), st), "viai_conv2d_fwd_p16")
+    else:
+        _lib.check(lib.viai_conv2d_fwd_amax(d["ref"], x.data_ptr(), _ptr(x2), wp.data_ptr(), _ptr(bias), out.data_ptr(), stat, act, _ptr(xa), st),
+                   "viai_conv2d_fwd")
+
+
+def _conv_bn_coef(lib, d, caps, x, x2, xp, xa, wp, bias, bn, cfg, y, coef, st):
+    """y = conv(x ++ x2) + bias and the BatchNorm coefficients (mean, invstd, scale, shift) behind it: from the batch statistics the conv kernel
+    leaves as partials (training; updates the running statistics) or from the running statistics (eval)"""
+    gamma, beta, rmean, rvar, nbt = bn
+    Cc = coef.shape[1]
+    if cfg["training"]:
+        stat = _scratch("stat", 2 * Cc * d["nblk"], y.device)
+        _conv_fwd(lib, d, x, x2, xp, xa, wp, bias, y, stat.data_ptr(), ACT_NONE, st)
+        _bn_finalize(lib, d, stat, y.numel() // Cc, Cc, gamma, beta, rmean, rvar, nbt, cfg, coef, st, lin=xp and bool(caps.p16 & P16_OK_FWD_LIN))
+    else:
+        _conv_fwd(lib, d, x, x2, xp, xa, wp, bias, y, 0, ACT_NONE, st)
+        _lib.check(lib.viai_bn_eval_coeffs(Cc, gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(), cfg["eps"], *_rows(coef), st),
+                   "viai_bn_eval_coeffs")
+
+
+# The BatchNorm-apply tails of _ConvBnAct.forward: z from the pre-BatchNorm map y in one pass, max |z| into za.  Each returns z and what the
+# backward needs beside (x, x2, weight, y, coef); a tail that also writes z as planes leaves them in cfg (z_p16: z itself; z_twin: a second tensor).
+# p16_out: the consumer stages pre-split pieces (networks.py asked conv_takes_p16) and the layer can write them (training, Cout % 32 == 0).
+
+def _tail_pool(lib, cfg, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
+    # BatchNorm + activation + max-pool: the post-activation map is never stored (the backward gathers its gradient from the pooled
+    # gradient and the argmax bytes inside the BatchNorm-backward passes)
+    N, OH, OW, Cout = dims
+    k_, s_, p_ = cfg["pool"]
+    PH, PW = (OH + 2 * p_ - k_) // s_ + 1, (OW + 2 * p_ - k_) // s_ + 1
+    sc, sh = _rows(coef)[2:]
+    z = torch.empty((N, PH, PW, Cout), device=y.device, dtype=torch.float32)
+    pidx = torch.empty((N, PH, PW, Cout), device=y.device, dtype=torch.uint8)
+    if p16_out and (k_, s_, p_) == (3, 2, 1) and z.numel() // 4 < (1 << 31) - (1 << 24):
+        zp = torch.empty_like(z)
+        pa = _amax_slot(y.device)
+        _lib.check(lib.viai_bn_act_maxpool_fwd_twin(y.data_ptr(), sc, sh, gamma.data_ptr(), beta.data_ptr(), N * OH * OW, z.data_ptr(), zp.data_ptr(),
+                                                    pidx.data_ptr(), N, OH, OW, Cout, k_, s_, p_, act, 0.2, za.data_ptr(), pa.data_ptr(), st),
+                   "viai_bn_act_maxpool_fwd_twin")
+        zp._viai_p16, zp._viai_amax = True, pa
+        cfg["z_twin"] = zp
+    else:
+        _lib.check(lib.viai_bn_act_maxpool_fwd(y.data_ptr(), sc, sh, z.data_ptr(), pidx.data_ptr(), N, OH, OW, Cout, k_, s_, p_, act, 0.2, za.data_ptr(), st),
+                   "viai_bn_act_maxpool_fwd")
+    return z, (pidx,)
+
+
+def _tail_res(lib, cfg, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
+    # BatchNorm + residual add + activation (ResNet BasicBlock); z is kept: the activation's mask needs the sum
+    N, OH, OW, Cout = dims
+    M = N * OH * OW
+    sc, sh = _rows(coef)[2:]
+    res = _c(res)
+    z = torch.empty_like(y)
+    ra = amax_of(res)
+    c4 = Cout // 4
+    if p16_out and ra is not None and c4 <= 256 and (c4 & (c4 - 1)) == 0:
+        # the next block's conv1 stages pre-split pieces: the join writes z twice (fp32 for the next join and the mask, P16 for the convs)
+        zp = torch.empty_like(y)
+        pa = _amax_slot(y.device)
+        _lib.check(lib.viai_bn_add_act_fwd_twin(y.data_ptr(), sc, sh, gamma.data_ptr(), beta.data_ptr(), M, res.data_ptr(), ra.data_ptr(), z.data_ptr(),
+                                                zp.data_ptr(), M, Cout, act, 0.2, za.data_ptr(), pa.data_ptr(), st), "viai_bn_add_act_fwd_twin")
+        zp._viai_p16, zp._viai_amax = True, pa
+        cfg["z_twin"] = zp
+    else:
+        _lib.check(lib.viai_bn_add_act_fwd_amax(y.data_ptr(), sc, sh, res.data_ptr(), z.data_ptr(), M, Cout, act, 0.2, za.data_ptr(), st), "viai_bn_add_act_fwd")
+    return z, (z,)
+
+
+def _tail_up(lib, cfg, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
+    # BatchNorm + activation + the F.interpolate behind the layer: the post-activation map is not stored (the backward gathers its
+    # gradient with the resize's backward and goes on from y)
+    N, OH, OW, Cout = dims
+    UH, UW = cfg["up"]
+    sc, sh = _rows(coef)[2:]
+    z = torch.empty((N, UH, UW, Cout), device=y.device, dtype=torch.float32)
+    if p16_out:
+        _lib.check(lib.viai_bn_act_bilinear_fwd_p16(y.data_ptr(), sc, sh, gamma.data_ptr(), beta.data_ptr(), N * OH * OW, z.data_ptr(), N, OH, OW, UH, UW,
+                                                    Cout, act, 0.2, za.data_ptr(), st), "viai_bn_act_bilinear_fwd_p16")
+        cfg["z_p16"] = True
+    else:
+        _lib.check(lib.viai_bn_act_bilinear_fwd_amax(y.data_ptr(), sc, sh, z.data_ptr(), N, OH, OW, UH, UW, Cout, act, 0.2, za.data_ptr(), st),
+                   "viai_bn_act_bilinear_fwd")
+    return z, ()
+
+
+def _tail_none(lib, cfg, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
+    N, OH, OW, Cout = dims
+    M = N * OH * OW
+    sc, sh = _rows(coef)[2:]
+    z = torch.empty_like(y)
+    if p16_out and act in (ACT_NONE, ACT_RELU, ACT_LRELU):
+        # z is written as the two fp16 planes, scale from the bound
+        _lib.check(lib.viai_bn_act_fwd_p16(y.data_ptr(), sc, sh, gamma.data_ptr(), beta.data_ptr(), M, z.data_ptr(), M, Cout, act, 0.2, za.data_ptr(), st),
+                   "viai_bn_act_fwd_p16")
+        cfg["z_p16"] = True
+    else:
+        _lib.check(lib.viai_bn_act_fwd_amax(y.data_ptr(), sc, sh, z.data_ptr(), M, Cout, act, 0.2, za.data_ptr(), st), "viai_bn_act_fwd")
+    return z, ()
+
+
+_TAILS = {"pool": _tail_pool, "res": _tail_res, "up": _tail_up, None: _tail_none}
+
+# what _ConvBnAct.backward needs of its forward beside the saved tensors (ctx.state; torch_ops.py builds one for its stand-in context)
+_LayerState = collections.namedtuple("_LayerState", "d cfg has_bn has_bias dims xa fused1 tail x_p16 x_twin_w xmask", defaults=(None, False, None, False, None, None))
 
 
 class _ConvBnAct(torch.autograd.Function):
@@ -580,6 +772,7 @@ class _ConvBnAct(torch.autograd.Function):
         dil, p2 = cfg.get("d", (1, 1)), cfg.get("p2", (-1, -1))
         d = conv_desc(N, IH, IW, C1, C2, Cout, kh, kw, cfg["s"][0], cfg["s"][1], cfg["p"][0], cfg["p"][1],
                       1 if transposed else 0, dil[0], dil[1], p2[0], p2[1])
+        caps = _caps(d)
         st = _stream()
         dev = x.device
         OH, OW = d["OH"], d["OW"]
@@ -590,48 +783,29 @@ class _ConvBnAct(torch.autograd.Function):
         has_bn = gamma is not None
         act = cfg["act"]
         training = cfg["training"]
-        f16f = d.get("fwd_f16")
-        if f16f is None:
-            f16f = d["fwd_f16"] = bool(lib.viai_conv2d_fwd_f16_ok(d["ref"]))
         twin = cfg.pop("x_twin", None)          # a pre-split copy of x beside the fp32 tensor (the residual join of a ResNet block writes both)
         # (both consumers of x must stage pieces: otherwise the weight gradient would decode the twin -- coarser scale -- although the exact fp32 x is at hand)
-        ctx.x_twin_w = None
-        if twin is not None and not xp and x2 is None and P16 and (p16_mask(d) & P16_OK_FWD_X) and (p16_mask(d) & P16_OK_WGRAD_X) and F16_BACKWARD:
-            x, xp = twin, True                  # the kernels read the planes; the gradient still goes to the fp32 tensor this op was applied to
-        elif twin is not None and not xp and x2 is None and P16 and (p16_mask(d) & P16_OK_WGRAD_X) and F16_BACKWARD and ctx.needs_input_grad[2]:
-            # only the weight-gradient kernel stages pieces (the stride-2 3 x 3 convs of ResNet-18 on 28 / 14 / 7-pixel maps: their forward runs on the
-            # gather kernel): the forward reads the fp32 tensor, the weight gradient the planes -- it splits nothing (1143 -> ~650 us per launch)
-            ctx.x_twin_w = twin
-        if xp and (x2 is not None or (p16_mask(d) & P16_OK_FWD_X) == 0):
-            x = p16_decode(x)                   # (a layer without a P16 loader: the networks of this package ask conv_takes_p16 first)
-            xp = False
-        if xp:
-            xa = amax_of(x)                     # the scale the planes were written with
-        else:
-            xa = _input_amax(x, x2, cfg.get("xa_in", (None, None)), st) if (f16f and F16_DYNAMIC) else None   # operand magnitude of the f16x2 split (forward and weight gradient)
-        ctx.xa = xa
-        ctx.x_p16 = xp
-
-        def conv_fwd(out, stat, act_):
-            if xp:
-                _lib.check(lib.viai_conv2d_fwd_p16(d["ref"], x.data_ptr(), wp.data_ptr(), _ptr(bias), out.data_ptr(), stat, act_, xa.data_ptr(), st), "viai_conv2d_fwd_p16")
-            else:
-                _lib.check(lib.viai_conv2d_fwd_amax(d["ref"], x.data_ptr(), _ptr(x2), wp.data_ptr(), _ptr(bias), out.data_ptr(), stat, act_, _ptr(xa), st),
-                           "viai_conv2d_fwd")
-        za = None
-        fused1 = False
-        if has_bn and training and bias is None and C1 + C2 == 1:
-            fused1 = d.get("cin1_bn")
-            if fused1 is None:
-                fused1 = d["cin1_bn"] = bool(lib.viai_conv2d_cin1_bn_ok(d["ref"]))
-        ctx.fused1 = fused1
+        x_twin_w = None
+        if twin is not None and not xp and x2 is None and P16 and (caps.p16 & P16_OK_WGRAD_X) and F16_BACKWARD:
+            if caps.p16 & P16_OK_FWD_X:
+                x, xp = twin, True              # the kernels read the planes; the gradient still goes to the fp32 tensor this op was applied to
+            elif ctx.needs_input_grad[2]:
+                # only the weight-gradient kernel stages pieces (the stride-2 3 x 3 convs of ResNet-18 on 28 / 14 / 7-pixel maps: their forward runs on the
+                # gather kernel): the forward reads the fp32 tensor, the weight gradient the planes -- it splits nothing (1143 -> ~650 us per launch)
+                x_twin_w = twin
+        x, xp, xa = _stage_input(d, caps, x, x2, xp, cfg, st)
+        fused1 = has_bn and training and bias is None and C1 + C2 == 1 and caps.cin1_bn
         xmask = cfg.get("xmask")
         if xmask is not None and not fused1:
             raise RuntimeError("conv_bn_act: xmask reached a layer that is not the fused Cin = 1 layer (conv_bn_act applies it up front otherwise)")
-        ctx.xmask = xmask
+        tail = "pool" if cfg.get("pool") is not None else ("res" if res is not None else ("up" if cfg.get("up") is not None else None))
+        if tail is not None and (not has_bn or fused1):
+            raise RuntimeError("conv_bn_act: residual / pool / upsample need a BatchNorm layer on the MFMA path")
+        za = None
         if fused1:
             # Cin = 1 conv + BatchNorm(train) + activation: the pre-BatchNorm tensor is never stored (recomputed from x where needed)
             coef = torch.empty((4, Cout), device=dev, dtype=torch.float32)
+            sc, sh = _rows(coef)[2:]
             stat = _scratch("stat", 2 * Cout * d["nblk"], dev)
             _lib.check(lib.viai_conv2d_cin1_bn_fwd(d["ref"], x.data_ptr(), _ptr(xmask), wp.data_ptr(), 0, stat.data_ptr(), 0, 0, 0, act, 0, st),
                        "viai_conv2d_cin1_bn_fwd")
@@ -639,249 +813,133 @@ class _ConvBnAct(torch.autograd.Function):
             z = torch.empty((N, OH, OW, Cout), device=dev, dtype=torch.float32)
             za = _amax_slot(dev)
             if cfg.get("p16_out") and P16 and act in (ACT_NONE, ACT_RELU, ACT_LRELU):
-                _lib.check(lib.viai_conv2d_cin1_bn_fwd_p16(d["ref"], x.data_ptr(), _ptr(xmask), wp.data_ptr(), 0, coef[2].data_ptr(), coef[3].data_ptr(),
-                                                           gamma.data_ptr(), beta.data_ptr(), M, z.data_ptr(), act, za.data_ptr(), st), "viai_conv2d_cin1_bn_fwd_p16")
+                _lib.check(lib.viai_conv2d_cin1_bn_fwd_p16(d["ref"], x.data_ptr(), _ptr(xmask), wp.data_ptr(), 0, sc, sh, gamma.data_ptr(), beta.data_ptr(), M,
+                                                           z.data_ptr(), act, za.data_ptr(), st), "viai_conv2d_cin1_bn_fwd_p16")
                 cfg["z_p16"] = True
             else:
-                _lib.check(lib.viai_conv2d_cin1_bn_fwd(d["ref"], x.data_ptr(), _ptr(xmask), wp.data_ptr(), 0, 0, coef[2].data_ptr(), coef[3].data_ptr(),
-                                                       z.data_ptr(), act, za.data_ptr(), st), "viai_conv2d_cin1_bn_fwd")
+                _lib.check(lib.viai_conv2d_cin1_bn_fwd(d["ref"], x.data_ptr(), _ptr(xmask), wp.data_ptr(), 0, 0, sc, sh, z.data_ptr(), act, za.data_ptr(), st),
+                           "viai_conv2d_cin1_bn_fwd")
             ctx.save_for_backward(x, None, weight, None, coef)
         elif has_bn:
             y = torch.empty((N, OH, OW, Cout), device=dev, dtype=torch.float32)
             coef = torch.empty((4, Cout), device=dev, dtype=torch.float32)   # mean, invstd, scale, shift
-            if training:
-                stat = _scratch("stat", 2 * Cout * d["nblk"], dev)
-                conv_fwd(y, stat.data_ptr(), ACT_NONE)
-                _bn_finalize(lib, d, stat, M, Cout, gamma, beta, rmean, rvar, nbt, cfg, coef, st, lin=xp and bool(p16_mask(d) & P16_OK_FWD_LIN))
-            else:
-                conv_fwd(y, 0, ACT_NONE)
-                _lib.check(lib.viai_bn_eval_coeffs(Cout, gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(),
-                                                   rvar.data_ptr(), cfg["eps"], coef[0].data_ptr(), coef[1].data_ptr(),
-                                                   coef[2].data_ptr(), coef[3].data_ptr(), st), "viai_bn_eval_coeffs")
+            _conv_bn_coef(lib, d, caps, x, x2, xp, xa, wp, bias, (gamma, beta, rmean, rvar, nbt), cfg, y, coef, st)
             za = _amax_slot(dev)
-            pool = cfg.get("pool")
-            if pool is not None:
-                # BatchNorm + activation + max-pool in one pass over y: the post-activation map is never stored (the backward gathers its
-                # gradient from the pooled gradient and the argmax bytes inside the BatchNorm-backward passes)
-                k_, s_, p_ = pool
-                PH, PW = (OH + 2 * p_ - k_) // s_ + 1, (OW + 2 * p_ - k_) // s_ + 1
-                z = torch.empty((N, PH, PW, Cout), device=dev, dtype=torch.float32)
-                pidx = torch.empty((N, PH, PW, Cout), device=dev, dtype=torch.uint8)
-                if cfg.get("p16_out") and P16 and training and Cout % 32 == 0 and (k_, s_, p_) == (3, 2, 1) and z.numel() // 4 < (1 << 31) - (1 << 24):
-                    zp = torch.empty_like(z)
-                    pa = _amax_slot(dev)
-                    _lib.check(lib.viai_bn_act_maxpool_fwd_twin(y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), gamma.data_ptr(), beta.data_ptr(), M,
-                                                                z.data_ptr(), zp.data_ptr(), pidx.data_ptr(), N, OH, OW, Cout, k_, s_, p_, act, 0.2,
-                                                                za.data_ptr(), pa.data_ptr(), st), "viai_bn_act_maxpool_fwd_twin")
-                    zp._viai_p16, zp._viai_amax = True, pa
-                    cfg["z_twin"] = zp
-                else:
-                    _lib.check(lib.viai_bn_act_maxpool_fwd(y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), z.data_ptr(), pidx.data_ptr(),
-                                                           N, OH, OW, Cout, k_, s_, p_, act, 0.2, za.data_ptr(), st), "viai_bn_act_maxpool_fwd")
-                ctx.save_for_backward(x, x2, weight, y, coef, pidx)
-            elif res is not None:
-                # BatchNorm + residual add + activation in one pass (ResNet BasicBlock); z is kept: the activation's mask needs the sum
-                res = _c(res)
-                z = torch.empty_like(y)
-                ra = amax_of(res)
-                c4 = Cout // 4
-                if (cfg.get("p16_out") and P16 and training and ra is not None and Cout % 32 == 0 and c4 <= 256 and (c4 & (c4 - 1)) == 0):
-                    # the next block's conv1 stages pre-split pieces: the join writes z twice (fp32 for the next join and the mask, P16 for the convs)
-                    zp = torch.empty_like(y)
-                    pa = _amax_slot(dev)
-                    _lib.check(lib.viai_bn_add_act_fwd_twin(y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), gamma.data_ptr(), beta.data_ptr(), M,
-                                                            res.data_ptr(), ra.data_ptr(), z.data_ptr(), zp.data_ptr(), M, Cout, act, 0.2,
-                                                            za.data_ptr(), pa.data_ptr(), st), "viai_bn_add_act_fwd_twin")
-                    zp._viai_p16, zp._viai_amax = True, pa
-                    cfg["z_twin"] = zp
-                else:
-                    _lib.check(lib.viai_bn_add_act_fwd_amax(y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), res.data_ptr(), z.data_ptr(),
-                                                            M, Cout, act, 0.2, za.data_ptr(), st), "viai_bn_add_act_fwd")
-                ctx.save_for_backward(x, x2, weight, y, coef, z)
-            elif cfg.get("up") is not None:
-                # BatchNorm + activation + the F.interpolate behind the layer in one pass over y: the post-activation map is not stored
-                # (the backward gathers its gradient with the resize's backward and goes on from y)
-                UH, UW = cfg["up"]
-                z = torch.empty((N, UH, UW, Cout), device=dev, dtype=torch.float32)
-                if cfg.get("p16_out") and P16 and training and Cout % 32 == 0:
-                    _lib.check(lib.viai_bn_act_bilinear_fwd_p16(y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), gamma.data_ptr(), beta.data_ptr(), M,
-                                                                z.data_ptr(), N, OH, OW, UH, UW, Cout, act, 0.2, za.data_ptr(), st), "viai_bn_act_bilinear_fwd_p16")
-                    cfg["z_p16"] = True
-                else:
-                    _lib.check(lib.viai_bn_act_bilinear_fwd_amax(y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), z.data_ptr(), N, OH, OW, UH, UW,
-                                                                 Cout, act, 0.2, za.data_ptr(), st), "viai_bn_act_bilinear_fwd")
-                ctx.save_for_backward(x, x2, weight, y, coef)
-            elif cfg.get("p16_out") and P16 and training and Cout % 32 == 0 and act in (ACT_NONE, ACT_RELU, ACT_LRELU):
-                # the consumer stages pre-split pieces (networks.py asked conv_takes_p16): z is written as the two fp16 planes, scale from the bound
-                z = torch.empty_like(y)
-                _lib.check(lib.viai_bn_act_fwd_p16(y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), gamma.data_ptr(), beta.data_ptr(), M, z.data_ptr(),
-                                                   M, Cout, act, 0.2, za.data_ptr(), st), "viai_bn_act_fwd_p16")
-                cfg["z_p16"] = True
-                ctx.save_for_backward(x, x2, weight, y, coef)
-            else:
-                z = torch.empty_like(y)
-                _lib.check(lib.viai_bn_act_fwd_amax(y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), z.data_ptr(),
-                                                    M, Cout, act, 0.2, za.data_ptr(), st), "viai_bn_act_fwd")
-                ctx.save_for_backward(x, x2, weight, y, coef)
-            ctx.tail = "pool" if pool is not None else ("res" if res is not None else ("up" if cfg.get("up") is not None else None))
+            p16_out = bool(cfg.get("p16_out") and P16 and training and Cout % 32 == 0)
+            z, extra = _TAILS[tail](lib, cfg, y, coef, gamma, beta, res, (N, OH, OW, Cout), act, p16_out, za, st)
+            ctx.save_for_backward(x, x2, weight, y, coef, *extra)
         else:
             z = torch.empty((N, OH, OW, Cout), device=dev, dtype=torch.float32)
-            conv_fwd(z, 0, act)
+            _conv_fwd(lib, d, x, x2, xp, xa, wp, bias, z, 0, act, st)
             if act == ACT_SIGMOID:
                 za = _const_amax(dev, 1.0)
             ctx.save_for_backward(x, x2, weight, z, None)
-        if not has_bn or fused1:
-            if res is not None or cfg.get("pool") is not None or cfg.get("up") is not None:
-                raise RuntimeError("conv_bn_act: residual / pool / upsample need a BatchNorm layer on the MFMA path")
-            ctx.tail = None
         cfg["za"] = za                       # conv_bn_act attaches it to the returned tensor
-        ctx.d = d
-        ctx.cfg = cfg
-        ctx.has_bn = has_bn
-        ctx.has_bias = bias is not None
-        ctx.dims = (N, IH, IW, C1, C2, Cout, OH, OW)
+        ctx.state = _LayerState(d, cfg, has_bn, bias is not None, (N, IH, IW, C1, C2, Cout, OH, OW), xa, fused1, tail, xp, x_twin_w, xmask)
         return z
 
     @staticmethod
     def backward(ctx, dz):
         lib = _lib.load()
-        x, x2, weight, y_or_z, coef = ctx.saved_tensors[:5]
-        d, cfg = ctx.d, ctx.cfg
-        N, IH, IW, C1, C2, Cout, OH, OW = ctx.dims
-        M = N * OH * OW
+        s = ctx.state
+        saved = ctx.saved_tensors
+        x, x2, weight, y_or_z, coef = saved[:5]
+        cfg, tail = s.cfg, s.tail
         st = _stream()
-        dev = dz.device
         addend = _take_addend(ctx)
         dz = _c(dz)
         act = cfg["act"]
         # (the pool tail takes two addends as well -- viai_bn_act_pool_bwd_amax2.  With the per-pixel apply pass, which gathered up to four windows per pixel,
         # two tensors to gather cost more than the add they save (103.5 against 102.2 ms on the vision-infused step); with the 2 x 2-block pass it is a
         # small gain: 102.17 -> 101.99, two same-box pairs)
-        if addend is not None and not ((ctx.tail == "res" and act != ACT_NONE and not ctx.fused1 and dz.numel() % 4 == 0) or (POOL_ADDENDS and ctx.tail == "pool" and ctx.has_bn)):
+        if addend is not None and not ((tail == "res" and act != ACT_NONE and not s.fused1 and dz.numel() % 4 == 0) or (POOL_ADDENDS and tail == "pool" and s.has_bn)):
             dz = dz + addend                              # no pass of this backward to fold the sum into
             addend = None
-        need_x, need_x2, need_w, need_b, need_g, need_be = ctx.needs_input_grad[:6]
-        gt = cfg.get("gt") or (None, None, None, None)       # in-place gradient targets (arena views)
-        dgamma = dbeta = None
-        amax = None
-        dy_p16 = False
-        dy_w = None                                    # dy as planes for the weight gradient only (see dy_tw below)
-        if ctx.fused1:
-            return _ConvBnAct._backward_cin1(ctx, lib, dz, x, weight, coef, st)
-        dres = None
-        if ctx.tail == "up":
-            UH, UW = cfg["up"]
-            dlo = torch.empty((N, OH, OW, Cout), device=dev, dtype=torch.float32)
-            _lib.check(lib.viai_bilinear_ac_bwd(dz.data_ptr(), dlo.data_ptr(), N, OH, OW, UH, UW, Cout, st), "viai_bilinear_ac_bwd")
-            dz = dlo
-        join = None                                    # (dz, addend, saved join output): the masked sum is made inside the BatchNorm backward's reduce pass
-        if ctx.tail == "res" and act == ACT_RELU and JOIN_FUSED and ctx.has_bn and P16 and F16_BACKWARD and Cout % 32 == 0 and (need_x or need_w):
-            pm_ = p16_mask(d)
-            f16d_ = d.get("dgrad_f16")
-            if f16d_ is None:
-                f16d_ = d["dgrad_f16"] = bool(lib.viai_conv2d_dgrad_f16_ok(d["ref"]))
-            f16w_ = d.get("wgrad_f16")
-            if f16w_ is None:
-                f16w_ = d["wgrad_f16"] = bool(lib.viai_conv2d_wgrad_f16_ok(d["ref"]))
-            # (exactly the layers whose dy the plain path below would write as planes: same condition)
-            if ((f16d_ and need_x) or (f16w_ and need_w)) and (not need_x or (f16d_ and pm_ & P16_OK_DGRAD_DY)) and (not need_w or (f16w_ and pm_ & P16_OK_WGRAD_DY)) \
-                    and not (need_b and ctx.has_bias and not cfg["training"]):
-                join = (dz, addend, ctx.saved_tensors[5])
-                dres = torch.empty_like(dz)
-                dz = dres
-                act = ACT_NONE
-        if ctx.tail == "res" and join is None:
-            # d/d(sum) through the activation (mask from the saved output); the same tensor is the residual branch's gradient
-            if act != ACT_NONE:
-                dres = torch.empty_like(dz)
-                if addend is not None:
-                    _lib.check(lib.viai_add_act_bwd_from_output(dz.data_ptr(), addend.data_ptr(), ctx.saved_tensors[5].data_ptr(), dres.data_ptr(), dz.numel(), act, 0.2,
-                                                                st), "viai_add_act_bwd_from_output")
-                else:
-                    _lib.check(lib.viai_act_bwd_from_output(dz.data_ptr(), ctx.saved_tensors[5].data_ptr(), dres.data_ptr(), dz.numel(), act, 0.2, st),
-                               "viai_act_bwd_from_output")
-                dz = dres
-            else:
-                dres = dz
-            act = ACT_NONE
-        if ctx.has_bn:
-            nblk = lib.viai_bn_bwd_blocks(M, Cout)
-            part = _scratch("bnpart", 2 * Cout * nblk, dev)
-            sums = _scratch("bnsums", 2 * Cout, dev)
-            acc_bn = gt[2] is not None and gt[3] is not None and need_g and need_be
-            if acc_bn:
-                pg, pb = gt[2], gt[3]
-            else:
-                dgamma = torch.empty(Cout, device=dev, dtype=torch.float32) if need_g else None
-                dbeta = torch.empty(Cout, device=dev, dtype=torch.float32) if need_be else None
-                pg, pb = dgamma, dbeta
-            dy = torch.empty_like(dz)
-            f16d = d.get("dgrad_f16")
-            if f16d is None:
-                f16d = d["dgrad_f16"] = bool(lib.viai_conv2d_dgrad_f16_ok(d["ref"]))
-            f16w = d.get("wgrad_f16")
-            if f16w is None:
-                f16w = d["wgrad_f16"] = bool(lib.viai_conv2d_wgrad_f16_ok(d["ref"]))
-            # max |dy|: operand scale of the f16x2 data- and weight-gradient kernels
-            amax = _amax_slot(dev) if (F16_BACKWARD and ((f16d and need_x) or (f16w and need_w))) else None
-            # dy pre-split (P16) when every kernel that reads it stages pieces: this layer's data gradient (if needed) and weight gradient
-            # (if needed); a bias gradient (column sums of dy) needs the fp32 tensor
-            pm = p16_mask(d)
-            dy_p16 = (P16 and amax is not None and Cout % 32 == 0 and act != ACT_SIGMOID and ctx.tail in (None, "up", "res")
-                      and (need_x or need_w) and (not need_x or (f16d and pm & P16_OK_DGRAD_DY)) and (not need_w or (f16w and pm & P16_OK_WGRAD_DY))
-                      and not (need_b and ctx.has_bias and not cfg["training"]))
-            # ... and where only the weight gradient does (its data-gradient kernel reads fp32): both forms in one apply pass
-            dy_tw = (not dy_p16 and P16 and amax is not None and Cout % 32 == 0 and act != ACT_SIGMOID and ctx.tail in (None, "up", "res")
-                     and need_x and need_w and f16w and bool(pm & P16_OK_WGRAD_DY) and not (need_b and ctx.has_bias and not cfg["training"]))
-            if dy_tw:
-                part = _scratch("bnpart", 3 * Cout * nblk, dev)
-                sums = _scratch("bnsums", 3 * Cout, dev)
-                dy_w = torch.empty_like(dz)
-                _lib.check(lib.viai_bn_act_bwd_p16_twin(dz.data_ptr(), y_or_z.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(),
-                                                        coef[2].data_ptr(), coef[3].data_ptr(), part.data_ptr(), sums.data_ptr(),
-                                                        _ptr(pg), _ptr(pb), dy_w.data_ptr(), dy.data_ptr(), M, Cout, act, 0.2,
-                                                        (1 if cfg["training"] else 0) | (2 if acc_bn else 0), amax.data_ptr(), st), "viai_bn_act_bwd_p16_twin")
-            elif join is not None:
-                if not dy_p16:
-                    raise RuntimeError("conv_bn_act backward: the fused join pass was chosen for a layer whose dy is not written as planes")
-                part = _scratch("bnpart", 3 * Cout * nblk, dev)
-                sums = _scratch("bnsums", 3 * Cout, dev)
-                _lib.check(lib.viai_bn_join_bwd_p16(join[0].data_ptr(), _ptr(join[1]), join[2].data_ptr(), dres.data_ptr(), y_or_z.data_ptr(),
-                                                    coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), part.data_ptr(), sums.data_ptr(),
-                                                    _ptr(pg), _ptr(pb), dy.data_ptr(), M, Cout, (1 if cfg["training"] else 0) | (2 if acc_bn else 0), amax.data_ptr(), st),
-                           "viai_bn_join_bwd_p16")
-            elif dy_p16:
-                part = _scratch("bnpart", 3 * Cout * nblk, dev)
-                sums = _scratch("bnsums", 3 * Cout, dev)
-                _lib.check(lib.viai_bn_act_bwd_p16(dz.data_ptr(), y_or_z.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(),
-                                                   coef[2].data_ptr(), coef[3].data_ptr(), part.data_ptr(), sums.data_ptr(),
-                                                   _ptr(pg), _ptr(pb), dy.data_ptr(), M, Cout, act, 0.2,
-                                                   (1 if cfg["training"] else 0) | (2 if acc_bn else 0), amax.data_ptr(), st), "viai_bn_act_bwd_p16")
-            elif ctx.tail == "pool":
-                k_, s_, p_ = cfg["pool"]
-                dy = torch.empty_like(y_or_z)
-                # (the pooled gradient may have arrived as two addends -- ops.fork2: the stem's output feeds layer1's conv1 and its first join -- summed on load)
-                _lib.check(lib.viai_bn_act_pool_bwd_amax2(dz.data_ptr(), _ptr(addend), ctx.saved_tensors[5].data_ptr(), N, OH, OW, k_, s_, p_, y_or_z.data_ptr(),
-                                                         coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(),
-                                                         part.data_ptr(), sums.data_ptr(), _ptr(pg), _ptr(pb), dy.data_ptr(), Cout, act, 0.2,
-                                                          (1 if cfg["training"] else 0) | (2 if acc_bn else 0), _ptr(amax), st), "viai_bn_act_pool_bwd")
-            else:
-                _lib.check(lib.viai_bn_act_bwd_amax(dz.data_ptr(), y_or_z.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(),
-                                                    coef[2].data_ptr(), coef[3].data_ptr(), part.data_ptr(), sums.data_ptr(),
-                                                    _ptr(pg), _ptr(pb), dy.data_ptr(), M, Cout, act, 0.2,
-                                                    (1 if cfg["training"] else 0) | (2 if acc_bn else 0), _ptr(amax), st), "viai_bn_act_bwd")
+        needs = ctx.needs_input_grad[:6]
+        if s.fused1:
+            return _backward_cin1(s, needs, lib, dz, x, weight, coef, st)
+        need_x, need_x2, need_w, need_b = needs[:4]
+        want_amax, form = False, DY_PLAIN
+        if s.has_bn:
+            want_amax, form = _dy_form(_caps(s.d), need_x, need_w, need_b, act, tail, s.has_bias, cfg["training"], s.dims[5], P16, F16_BACKWARD, JOIN_FUSED)
+        # 1. the gradient through the tail, down to the BatchNorm's output
+        dz, dres, act = _tail_bwd(lib, s, form, act, dz, addend, saved, st)
+        # 2. through BatchNorm + activation (or the activation alone): dy, the gradient of the conv's output, in the chosen form
+        dgamma = dbeta = amax = dy_w = None                 # dy_w: dy once more as planes, for the weight gradient only (DY_TWIN)
+        if s.has_bn:
+            dy, dy_w, amax, dgamma, dbeta = _bn_bwd(lib, s, form, want_amax, act, dz, addend, saved, dres, needs, st)
         elif act == ACT_NONE:
             dy = dz
         else:
             dy = torch.empty_like(dz)
-            _lib.check(lib.viai_act_bwd_from_output(dz.data_ptr(), y_or_z.data_ptr(), dy.data_ptr(), dz.numel(), act,
-                                                    0.2, st), "viai_act_bwd_from_output")
-        xw, xwa, xwp = x, ctx.xa, ctx.x_p16
-        if ctx.x_twin_w is not None and need_w:
-            xw, xwa, xwp = ctx.x_twin_w, amax_of(ctx.x_twin_w), True          # planes for the weight gradient (the forward read the fp32 tensor)
-        dx, dx2, dw, db = _conv_grads(lib, d, cfg, ctx.dims, ctx.has_bn, ctx.has_bias, (need_x, need_x2, need_w, need_b), xwa,
-                                      xw, x2, weight, dy, amax, st, dy_p16=dy_p16, x_p16=xwp, dy_w=dy_w)
+            _lib.check(lib.viai_act_bwd_from_output(dz.data_ptr(), y_or_z.data_ptr(), dy.data_ptr(), dz.numel(), act, 0.2, st), "viai_act_bwd_from_output")
+        # 3. the conv's own gradients
+        xw, xwa, xwp = x, s.xa, s.x_p16
+        if s.x_twin_w is not None and need_w:
+            xw, xwa, xwp = s.x_twin_w, amax_of(s.x_twin_w), True          # planes for the weight gradient (the forward read the fp32 tensor)
+        dx, dx2, dw, db = _conv_grads(lib, s.d, cfg, s.dims, s.has_bn, s.has_bias, (need_x, need_x2, need_w, need_b), xwa,
+                                      xw, x2, weight, dy, amax, st, dy_p16=form in (DY_PLANES, DY_JOIN), x_p16=xwp, dy_w=dy_w)
         return dx, dx2, dw, db, dgamma, dbeta, None, None, None, dres, None
+
+
+def _tail_bwd(lib, s, form, act, dz, addend, saved, st):
+    """the incoming gradient taken back through the layer's tail: (dz at the BatchNorm's output, the residual branch's gradient or None, the
+    activation the BatchNorm backward still has to take).  The pool tail's gather and the fused join's masked sum happen inside the BatchNorm
+    backward: nothing to launch here (the join only gets its dres tensor)."""
+    if s.tail == "up":
+        N, _, _, _, _, Cout, OH, OW = s.dims
+        UH, UW = s.cfg["up"]
+        dlo = torch.empty((N, OH, OW, Cout), device=dz.device, dtype=torch.float32)
+        _lib.check(lib.viai_bilinear_ac_bwd(dz.data_ptr(), dlo.data_ptr(), N, OH, OW, UH, UW, Cout, st), "viai_bilinear_ac_bwd")
+        return dlo, None, act
+    if s.tail != "res":
+        return dz, None, act
+    if form == DY_JOIN:
+        return dz, torch.empty_like(dz), ACT_NONE
+    if act == ACT_NONE:
+        return dz, dz, ACT_NONE
+    # d/d(sum) through the activation (mask from the saved output); the same tensor is the residual branch's gradient
+    dres = torch.empty_like(dz)
+    if addend is not None:
+        _lib.check(lib.viai_add_act_bwd_from_output(dz.data_ptr(), addend.data_ptr(), saved[5].data_ptr(), dres.data_ptr(), dz.numel(), act, 0.2, st),
+                   "viai_add_act_bwd_from_output")
+    else:
+        _lib.check(lib.viai_act_bwd_from_output(dz.data_ptr(), saved[5].data_ptr(), dres.data_ptr(), dz.numel(), act, 0.2, st), "viai_act_bwd_from_output")
+    return dres, dres, ACT_NONE
+
+
+def _bn_bwd(lib, s, form, want_amax, act, dz, addend, saved, dres, needs, st):
+    """BatchNorm + activation backward of a _ConvBnAct layer, dy written in the form _dy_form chose: (dy, dy_w, amax, dgamma, dbeta)"""
+    y, coef = saved[3], saved[4]
+    N, _, _, _, _, Cout, OH, OW = s.dims
+    M = N * OH * OW
+    dev = dz.device
+    nblk = lib.viai_bn_bwd_blocks(M, Cout)
+    rows = 2 if form in (DY_PLAIN, DY_POOL) else 3       # (the passes that write planes reduce max |dy| per channel as well)
+    part = _scratch("bnpart", rows * Cout * nblk, dev)
+    sums = _scratch("bnsums", rows * Cout, dev)
+    pg, pb, dgamma, dbeta, flags = _bn_targets(s.cfg.get("gt") or (None, None, None, None), needs[4], needs[5], s.cfg["training"], Cout, dev)
+    dy = torch.empty_like(y if form == DY_POOL else dz)
+    amax = _amax_slot(dev) if want_amax else None
+    dy_w = None
+    mid = (*_rows(coef), part.data_ptr(), sums.data_ptr(), _ptr(pg), _ptr(pb))
+    if form == DY_TWIN:
+        dy_w = torch.empty_like(dz)
+        _lib.check(lib.viai_bn_act_bwd_p16_twin(dz.data_ptr(), y.data_ptr(), *mid, dy_w.data_ptr(), dy.data_ptr(), M, Cout, act, 0.2, flags, amax.data_ptr(), st),
+                   "viai_bn_act_bwd_p16_twin")
+    elif form == DY_JOIN:
+        _lib.check(lib.viai_bn_join_bwd_p16(dz.data_ptr(), _ptr(addend), saved[5].data_ptr(), dres.data_ptr(), y.data_ptr(), *mid, dy.data_ptr(), M, Cout,
+                                            flags, amax.data_ptr(), st), "viai_bn_join_bwd_p16")
+    elif form == DY_PLANES:
+        _lib.check(lib.viai_bn_act_bwd_p16(dz.data_ptr(), y.data_ptr(), *mid, dy.data_ptr(), M, Cout, act, 0.2, flags, amax.data_ptr(), st), "viai_bn_act_bwd_p16")
+    elif form == DY_POOL:
+        k_, s_, p_ = s.cfg["pool"]
+        # (the pooled gradient may have arrived as two addends -- ops.fork2: the stem's output feeds layer1's conv1 and its first join -- summed on load)
+        _lib.check(lib.viai_bn_act_pool_bwd_amax2(dz.data_ptr(), _ptr(addend), saved[5].data_ptr(), N, OH, OW, k_, s_, p_, y.data_ptr(), *mid, dy.data_ptr(),
+                                                  Cout, act, 0.2, flags, _ptr(amax), st), "viai_bn_act_pool_bwd")
+    else:
+        _lib.check(lib.viai_bn_act_bwd_amax(dz.data_ptr(), y.data_ptr(), *mid, dy.data_ptr(), M, Cout, act, 0.2, flags, _ptr(amax), st), "viai_bn_act_bwd")
+    return dy, dy_w, amax, dgamma, dbeta
 
 
 # The first layer's weight gradient is the LAST launch of a backward: on the side stream it lengthens the tail the main chain waits for at the join in front
@@ -890,27 +948,20 @@ class _ConvBnAct(torch.autograd.Function):
 CIN1_WGRAD_MAIN = True
 
 
-def _backward_cin1(ctx, lib, dz, x, weight, coef, st):
+def _backward_cin1(s, needs, lib, dz, x, weight, coef, st):
     """backward of the fused Cin = 1 conv + BatchNorm(train) + activation layer: y is recomputed from x; dy is written to memory only
     when a data gradient needs it (the frozen-D pass of the G step), the weight gradient forms it on the fly."""
-    d, cfg = ctx.d, ctx.cfg
-    N, IH, IW, C1, C2, Cout, OH, OW = ctx.dims
-    M = N * OH * OW
+    d, cfg, xmask = s.d, s.cfg, s.xmask
+    N, IH, IW, C1, C2, Cout, OH, OW = s.dims
     dev = dz.device
     act = cfg["act"]
-    need_x, _, need_w, _, need_g, need_be = ctx.needs_input_grad[:6]
+    need_x, _, need_w, _, need_g, need_be = needs
     gt = cfg.get("gt") or (None, None, None, None)
     wp = _packed(weight, d, 0, st)
+    mean, invstd, sc, sh = _rows(coef)
     part = _scratch("bnpart1", 2 * Cout * d["nblk"], dev)
     sums = torch.empty(2 * Cout, device=dev, dtype=torch.float32)     # private: the trailing weight gradient reads it
-    acc_bn = gt[2] is not None and gt[3] is not None and need_g and need_be
-    dgamma = dbeta = None
-    if acc_bn:
-        pg, pb = gt[2], gt[3]
-    else:
-        dgamma = torch.empty(Cout, device=dev, dtype=torch.float32) if need_g else None
-        dbeta = torch.empty(Cout, device=dev, dtype=torch.float32) if need_be else None
-        pg, pb = dgamma, dbeta
+    pg, pb, dgamma, dbeta, flags = _bn_targets(gt, need_g, need_be, cfg["training"], Cout, dev)
     # the data gradient straight from dz (viai_conv2d_cin1_bn_dgrad).  Windows of one row (D.conv1: 1 x 4, the frozen-D pass of the G step)
     # take the single-pass kernel -- thread = output pixel, dz read once, no dy tensor: 55 + 80 us -> one pass over dz.  Other windows map
     # threads to INPUT pixels and recompute y per contributing output pixel: measured SLOWER than writing dy once with the recomputing
@@ -918,41 +969,27 @@ def _backward_cin1(ctx, lib, dz, x, weight, coef, st):
     one_row = (cfg["k"][0] == 1 and cfg["s"][0] == 1 and cfg["p"][0] == 0 and not cfg["transposed"])
     fused_dx = need_x and os.environ.get("VIAI_CIN1_BN_DGRAD", "1" if one_row else "0") != "0"
     dy = torch.empty_like(dz) if (need_x and not fused_dx) else None
-    xmask = ctx.xmask
-    _lib.check(lib.viai_conv2d_cin1_bn_bwd(d["ref"], x.data_ptr(), _ptr(xmask), wp.data_ptr(), 0, dz.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(),
-                                           coef[2].data_ptr(), coef[3].data_ptr(), part.data_ptr(), sums.data_ptr(), _ptr(pg), _ptr(pb),
-                                           _ptr(dy), act, 1 | (2 if acc_bn else 0), st), "viai_conv2d_cin1_bn_bwd")
+    _lib.check(lib.viai_conv2d_cin1_bn_bwd(d["ref"], x.data_ptr(), _ptr(xmask), wp.data_ptr(), 0, dz.data_ptr(), mean, invstd, sc, sh, part.data_ptr(),
+                                           sums.data_ptr(), _ptr(pg), _ptr(pb), _ptr(dy), act, flags, st), "viai_conv2d_cin1_bn_bwd")
     dw = dx = None
     if need_w:
         acc_w = gt[0] is not None
         dw = gt[0] if acc_w else torch.empty_like(weight)
-
-        def wgrad(stream_obj, handle):
-            ws = _scratch("wgrad", d["ws_floats"], dev, stream_obj) if stream_obj is not None else _scratch("wgrad", d["ws_floats"], dev)
-            _lib.check(lib.viai_conv2d_cin1_bn_wgrad(d["ref"], x.data_ptr(), _ptr(xmask), wp.data_ptr(), 0, dz.data_ptr(), coef[0].data_ptr(),
-                                                     coef[2].data_ptr(), coef[3].data_ptr(), sums.data_ptr(), ws.data_ptr(), dw.data_ptr(),
-                                                     1 if acc_w else 0, act, handle), "viai_conv2d_cin1_bn_wgrad")
-        if WGRAD_STREAM is not None and acc_w and not CIN1_WGRAD_MAIN:
-            ev = torch.cuda.Event()
-            ev.record()
-            WGRAD_STREAM.wait_event(ev)
-            wgrad(WGRAD_STREAM, WGRAD_STREAM.cuda_stream)
+        side, handle = _wgrad_side(acc_w and not CIN1_WGRAD_MAIN, st)
+        ws = _scratch("wgrad", d["ws_floats"], dev, side)
+        _lib.check(lib.viai_conv2d_cin1_bn_wgrad(d["ref"], x.data_ptr(), _ptr(xmask), wp.data_ptr(), 0, dz.data_ptr(), mean, sc, sh, sums.data_ptr(),
+                                                 ws.data_ptr(), dw.data_ptr(), 1 if acc_w else 0, act, handle), "viai_conv2d_cin1_bn_wgrad")
+        if side is not None:
             _deferred.append((x, dz, weight, wp, coef, sums, xmask))
-        else:
-            wgrad(None, st)
         if acc_w:
             dw = None
-        if GRAD_HOOKS:
-            hook = GRAD_HOOKS.get(weight.data_ptr())
-            if hook is not None:
-                hook()
+        _grad_ready(weight)
     if need_x:
         dx = torch.empty((N, IH, IW, C1), device=dev, dtype=torch.float32)
         wpd = _packed(weight, d, 1, st)
         if fused_dx:
-            _lib.check(lib.viai_conv2d_cin1_bn_dgrad(d["ref"], x.data_ptr(), _ptr(xmask), wpd.data_ptr(), dz.data_ptr(), coef[0].data_ptr(),
-                                                     coef[2].data_ptr(), coef[3].data_ptr(), sums.data_ptr(), dx.data_ptr(), act, st),
-                       "viai_conv2d_cin1_bn_dgrad")
+            _lib.check(lib.viai_conv2d_cin1_bn_dgrad(d["ref"], x.data_ptr(), _ptr(xmask), wpd.data_ptr(), dz.data_ptr(), mean, sc, sh, sums.data_ptr(),
+                                                     dx.data_ptr(), act, st), "viai_conv2d_cin1_bn_dgrad")
         else:
             _lib.check(lib.viai_conv2d_dgrad(d["ref"], dy.data_ptr(), wpd.data_ptr(), dx.data_ptr(), 0, st), "viai_conv2d_dgrad")
         if xmask is not None:                                   # d/ds of conv(s * mask)
@@ -961,19 +998,13 @@ def _backward_cin1(ctx, lib, dz, x, weight, coef, st):
     return dx, None, dw, None, dgamma, dbeta, None, None, None, None, None
 
 
-_ConvBnAct._backward_cin1 = staticmethod(_backward_cin1)
-
-
 def _cin1_fused_applies(x, weight, bias, bn, kernel, stride, padding, transposed, training):
     """will this call take the fused Cin = 1 conv + BatchNorm(train) layer?  (the predicate of _ConvBnAct.forward)"""
     if bn is None or not training or bias is not None or x.shape[3] != 1 or not isinstance(bn, torch.nn.modules.batchnorm._BatchNorm):
         return False
     Cout = weight.shape[1] if transposed else weight.shape[0]
     d = conv_desc(x.shape[0], x.shape[1], x.shape[2], 1, 0, Cout, kernel[0], kernel[1], stride[0], stride[1], padding[0], padding[1], 1 if transposed else 0)
-    f = d.get("cin1_bn")
-    if f is None:
-        f = d["cin1_bn"] = bool(_lib.load().viai_conv2d_cin1_bn_ok(d["ref"]))
-    return f
+    return _caps(d).cin1_bn
 
 
 def conv_bn_act(x, weight, bias=None, bn=None, *, kernel, stride=(1, 1), padding=(0, 0), transposed=False,
@@ -1090,33 +1121,12 @@ class _ConvBnActCout1(torch.autograd.Function):
             _range_scan("weight", w1, F16_WEIGHT_LIMIT)
         wp1 = _packed(w1, d, 0, st)
         wp2 = _packed(w2, d2, 0, st)
-        f16f = d.get("fwd_f16")
-        if f16f is None:
-            f16f = d["fwd_f16"] = bool(lib.viai_conv2d_fwd_f16_ok(d["ref"]))
-        if xp and (x2 is not None or (p16_mask(d) & P16_OK_FWD_X) == 0):
-            x = p16_decode(x)
-            xp = False
-        if xp:
-            xa = amax_of(x)
-        else:
-            xa = _input_amax(x, x2, cfg.get("xa_in", (None, None)), st) if (f16f and F16_DYNAMIC) else None
+        caps = _caps(d)
+        x, xp, xa = _stage_input(d, caps, x, x2, xp, cfg, st)
         y = torch.empty((N, OH, OW, Cmid), device=dev, dtype=torch.float32)
         coef = torch.empty((4, Cmid), device=dev, dtype=torch.float32)       # mean, invstd, scale, shift
-
-        def conv_fwd(stat):
-            if xp:
-                _lib.check(lib.viai_conv2d_fwd_p16(d["ref"], x.data_ptr(), wp1.data_ptr(), _ptr(b1), y.data_ptr(), stat, ACT_NONE, xa.data_ptr(), st), "viai_conv2d_fwd_p16")
-            else:
-                _lib.check(lib.viai_conv2d_fwd_amax(d["ref"], x.data_ptr(), _ptr(x2), wp1.data_ptr(), _ptr(b1), y.data_ptr(), stat, ACT_NONE, _ptr(xa), st), "viai_conv2d_fwd")
-        if cfg["training"]:
-            stat = _scratch("stat", 2 * Cmid * d["nblk"], dev)
-            conv_fwd(stat.data_ptr())
-            _bn_finalize(lib, d, stat, M, Cmid, gamma, beta, rmean, rvar, nbt, cfg, coef, st, lin=xp and bool(p16_mask(d) & P16_OK_FWD_LIN))
-        else:
-            conv_fwd(0)
-            _lib.check(lib.viai_bn_eval_coeffs(Cmid, gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(), cfg["eps"],
-                                               coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), st),
-                       "viai_bn_eval_coeffs")
+        _conv_bn_coef(lib, d, caps, x, x2, xp, xa, wp1, b1, (gamma, beta, rmean, rvar, nbt), cfg, y, coef, st)
+        sc, sh = _rows(coef)[2:]
         p = torch.empty((N, OH, OW, 1), device=dev, dtype=torch.float32)
         if PAIR_FWD_FUSED and Cmid <= 64:
             # BatchNorm + activation applied where the one-channel conv loads y: no z at all.  `cout1_pair_fwd_kernel` reads every input
@@ -1125,18 +1135,18 @@ class _ConvBnActCout1(torch.autograd.Function):
             # Standalone (tools/profile_pair.py): G.conv6_1 -> conv6_2 (32 channels, 256 x 256) 62 us against 46 + 57 for the two
             # launches; D.conv3 -> conv4 (512 channels on 64 x 32 maps) 67 us against 24 + 38 -- a whole wave per pixel leaves four
             # lane groups per block and 12 dependent load rounds each, so wide layers keep the two launches
-            _lib.check(lib.viai_pair_cout1_fwd(d2["ref"], y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), cfg["act"], wp2.data_ptr(),
+            _lib.check(lib.viai_pair_cout1_fwd(d2["ref"], y.data_ptr(), sc, sh, cfg["act"], wp2.data_ptr(),
                                                _ptr(b2), p.data_ptr(), cfg["act2"], st), "viai_pair_cout1_fwd")
         elif PAIR_FWD_DOTS:
             # wide front layers (D.conv3 -> conv4): one grid-stride pass over y leaves the nine tap products of every pixel, a gather sums
             # them: no z, y read once (was: bn_act_fwd 22 us + the row-run forward 36 us on the 67 MB tensor)
             ws = _scratch("pairdots", 9 * M, dev)
-            _lib.check(lib.viai_pair_cout1_fwd_dots(d2["ref"], y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), cfg["act"], wp2.data_ptr(),
+            _lib.check(lib.viai_pair_cout1_fwd_dots(d2["ref"], y.data_ptr(), sc, sh, cfg["act"], wp2.data_ptr(),
                                                     _ptr(b2), ws.data_ptr(), p.data_ptr(), cfg["act2"], st), "viai_pair_cout1_fwd_dots")
         else:
             # z exists only between these two launches: the backward works from y
             z = torch.empty_like(y)
-            _lib.check(lib.viai_bn_act_fwd(y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), z.data_ptr(), M, Cmid, cfg["act"], 0.2, st),
+            _lib.check(lib.viai_bn_act_fwd(y.data_ptr(), sc, sh, z.data_ptr(), M, Cmid, cfg["act"], 0.2, st),
                        "viai_bn_act_fwd")
             _lib.check(lib.viai_conv2d_fwd(d2["ref"], z.data_ptr(), 0, wp2.data_ptr(), _ptr(b2), p.data_ptr(), 0, cfg["act2"], st),
                        "viai_conv2d_fwd")
@@ -1179,16 +1189,10 @@ class _ConvBnActCout1(torch.autograd.Function):
             if ctx.has_bias2 and need_b2:
                 acc_b2 = gt2[1] is not None
                 db2 = gt2[1] if acc_b2 else torch.empty(1, device=dev, dtype=torch.float32)
-            side = WGRAD_STREAM if (WGRAD_STREAM is not None and acc_w2 and (acc_b2 or db2 is None)) else None
-            if side is not None:
-                ev = torch.cuda.Event()
-                ev.record()
-                side.wait_event(ev)
-            handle = side.cuda_stream if side is not None else st
-            ws = _scratch("wgrad", d2["ws_floats"] + lib.viai_colsum_blocks(M, 1) + 8, dev, side) if side is not None else \
-                _scratch("wgrad", d2["ws_floats"] + lib.viai_colsum_blocks(M, 1) + 8, dev)
+            side, handle = _wgrad_side(acc_w2 and (acc_b2 or db2 is None), st)
+            ws = _scratch("wgrad", d2["ws_floats"] + lib.viai_colsum_blocks(M, 1) + 8, dev, side)
             if need_w2:
-                _lib.check(lib.viai_pair_cout1_wgrad(d2["ref"], y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), cfg["act"], du.data_ptr(),
+                _lib.check(lib.viai_pair_cout1_wgrad(d2["ref"], y.data_ptr(), *_rows(coef)[2:], cfg["act"], du.data_ptr(),
                                                      ws.data_ptr(), dw2.data_ptr(), 1 if acc_w2 else 0, handle), "viai_pair_cout1_wgrad")
             if db2 is not None:
                 _lib.check(lib.viai_colsum(du.data_ptr(), M, 1, ws[d2["ws_floats"]:].data_ptr(), db2.data_ptr(), 1 if acc_b2 else 0, handle),
@@ -1203,37 +1207,19 @@ class _ConvBnActCout1(torch.autograd.Function):
         nblk = d2.get("pair_blk")
         if nblk is None:
             nblk = d2["pair_blk"] = int(lib.viai_pair_cout1_bn_bwd_blocks(d2["ref"]))
-        part = _scratch("bnpart", 2 * Cmid * nblk, dev)
-        sums = _scratch("bnsums", 2 * Cmid, dev)
-        acc_bn = gt[2] is not None and gt[3] is not None and need_g and need_be
-        dgamma = dbeta = None
-        if acc_bn:
-            pg, pb = gt[2], gt[3]
-        else:
-            dgamma = torch.empty(Cmid, device=dev, dtype=torch.float32) if need_g else None
-            dbeta = torch.empty(Cmid, device=dev, dtype=torch.float32) if need_be else None
-            pg, pb = dgamma, dbeta
-        f16d = d.get("dgrad_f16")
-        if f16d is None:
-            f16d = d["dgrad_f16"] = bool(lib.viai_conv2d_dgrad_f16_ok(d["ref"]))
-        f16w = d.get("wgrad_f16")
-        if f16w is None:
-            f16w = d["wgrad_f16"] = bool(lib.viai_conv2d_wgrad_f16_ok(d["ref"]))
-        amax = _amax_slot(dev) if (F16_BACKWARD and ((f16d and (need_x or need_x2)) or (f16w and need_w1))) else None
+        # (this op counts either source's gradient as the data gradient; it has no pass that writes both forms: planes or fp32)
+        want_amax, form = _dy_form(_caps(d), need_x or need_x2, need_w1, need_b1, cfg["act"], None, ctx.has_bias, cfg["training"], Cmid, P16, F16_BACKWARD, JOIN_FUSED)
+        dy_p16 = form == DY_PLANES
+        rows = 3 if dy_p16 else 2
+        part = _scratch("bnpart", rows * Cmid * nblk, dev)
+        sums = _scratch("bnsums", rows * Cmid, dev)
+        pg, pb, dgamma, dbeta, flags = _bn_targets(gt, need_g, need_be, cfg["training"], Cmid, dev)
+        amax = _amax_slot(dev) if want_amax else None
         want_dy = need_x or need_x2 or need_w1 or (need_b1 and ctx.has_bias)
         dy = torch.empty_like(y) if want_dy else None
-        pm = p16_mask(d)
-        nx = need_x or need_x2
-        dy_p16 = (P16 and want_dy and amax is not None and Cmid % 32 == 0 and cfg["act"] != ACT_SIGMOID and (nx or need_w1)
-                  and (not nx or (f16d and pm & P16_OK_DGRAD_DY)) and (not need_w1 or (f16w and pm & P16_OK_WGRAD_DY))
-                  and not (need_b1 and ctx.has_bias and not cfg["training"]))
-        if dy_p16:
-            part = _scratch("bnpart", 3 * Cmid * nblk, dev)
-            sums = _scratch("bnsums", 3 * Cmid, dev)
         fn = lib.viai_pair_cout1_bn_bwd_p16 if dy_p16 else lib.viai_pair_cout1_bn_bwd
-        _lib.check(fn(d2["ref"], du.data_ptr(), wp2.data_ptr(), y.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(),
-                      coef[2].data_ptr(), coef[3].data_ptr(), cfg["act"], part.data_ptr(), sums.data_ptr(), _ptr(pg), _ptr(pb),
-                      _ptr(dy), (1 if cfg["training"] else 0) | (2 if acc_bn else 0), _ptr(amax), st), "viai_pair_cout1_bn_bwd")
+        _lib.check(fn(d2["ref"], du.data_ptr(), wp2.data_ptr(), y.data_ptr(), *_rows(coef), cfg["act"], part.data_ptr(), sums.data_ptr(), _ptr(pg), _ptr(pb),
+                      _ptr(dy), flags, _ptr(amax), st), "viai_pair_cout1_bn_bwd")
         dx = dx2 = dw1 = db1 = None
         if want_dy:
             dx, dx2, dw1, db1 = _conv_grads(lib, d, cfg, ctx.dims, True, ctx.has_bias, (need_x, need_x2, need_w1, need_b1), ctx.xa,

@@ -24,7 +24,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from . import _lib, ops
+from . import ops
 
 __all__ = ["conv_bn_act"]
 
@@ -32,9 +32,10 @@ __all__ = ["conv_bn_act"]
 class _Ctx:
     """what ops._ConvBnAct.forward / backward need of an autograd context"""
 
-    def __init__(self, needs):
+    def __init__(self, needs, state=None, saved=()):
         self.needs_input_grad = tuple(needs)
-        self.saved_tensors = ()
+        self.state = state
+        self.saved_tensors = saved
 
     def save_for_backward(self, *tensors):
         self.saved_tensors = tensors
@@ -66,12 +67,11 @@ def _conv_bn_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
     rm = running_mean.clone() if track else None
     rv = running_var.clone() if track else None
     z = ops._ConvBnAct.forward(ctx, x, None, weight, bias, gamma, beta, rm, rv, None, None, cfg)
-    saved = ctx.saved_tensors
-    y, coef = saved[3], saved[4]
+    y, coef, xa = ctx.saved_tensors[3], ctx.saved_tensors[4], ctx.state.xa
     dev = x.device
     # outputs must not alias each other: without BatchNorm the saved map IS z (the backward op takes z for it)
     return (z, y if (y is not None and y is not z) else _empty(dev), coef if coef is not None else _empty(dev),
-            ctx.xa.reshape(-1).clone() if ctx.xa is not None else _empty(dev), rm if track else _empty(dev), rv if track else _empty(dev))
+            xa.reshape(-1).clone() if xa is not None else _empty(dev), rm if track else _empty(dev), rv if track else _empty(dev))
 
 
 def _out_hw(x, weight, kernel, stride, padding, transposed):
@@ -96,9 +96,7 @@ def _(x, weight, bias, gamma, beta, running_mean, running_var, kernel, stride, p
 def _conv_bn_act_backward(dz: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, z: torch.Tensor, y: torch.Tensor, coef: torch.Tensor, xa: torch.Tensor,
                           has_bias: bool, kernel: List[int], stride: List[int], padding: List[int], transposed: bool, act: int, training: bool,
                           momentum: float, eps: float, needs: List[bool]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    lib = _lib.load()
     has_bn = coef.numel() > 0
-    ctx = _Ctx((needs[0], False, needs[1], needs[2] and has_bias, needs[3] and has_bn, needs[4] and has_bn, False, False, False, False, False))
     cfg = _cfg(kernel, stride, padding, transposed, act, training, momentum, eps)
     N, IH, IW, C1 = x.shape
     cout = weight.shape[1] if transposed else weight.shape[0]
@@ -106,12 +104,11 @@ def _conv_bn_act_backward(dz: torch.Tensor, x: torch.Tensor, weight: torch.Tenso
     if C1 == 4 and 1 < cin_w < 4:
         C1 = cin_w
     d = ops.conv_desc(N, IH, IW, C1, 0, cout, kernel[0], kernel[1], stride[0], stride[1], padding[0], padding[1], 1 if transposed else 0)
-    fused1 = bool(has_bn and training and not has_bias and C1 == 1 and lib.viai_conv2d_cin1_bn_ok(d["ref"]))
-    ctx.d, ctx.cfg, ctx.has_bn, ctx.has_bias = d, cfg, has_bn, has_bias
-    ctx.dims = (N, IH, IW, C1, 0, cout, d["OH"], d["OW"])
-    ctx.fused1, ctx.tail, ctx.x_p16, ctx.x_twin_w, ctx.xmask = fused1, None, False, None, None
-    ctx.xa = xa.reshape(1) if xa.numel() else None
-    ctx.saved_tensors = (x, None, weight, None if fused1 else (y if has_bn else z), coef if has_bn else None)
+    fused1 = bool(has_bn and training and not has_bias and C1 == 1 and ops._caps(d).cin1_bn)
+    state = ops._LayerState(d=d, cfg=cfg, has_bn=has_bn, has_bias=has_bias, dims=(N, IH, IW, C1, 0, cout, d["OH"], d["OW"]),
+                            xa=xa.reshape(1) if xa.numel() else None, fused1=fused1)
+    ctx = _Ctx((needs[0], False, needs[1], needs[2] and has_bias, needs[3] and has_bn, needs[4] and has_bn, False, False, False, False, False), state,
+               (x, None, weight, None if fused1 else (y if has_bn else z), coef if has_bn else None))
     g = ops._ConvBnAct.backward(ctx, dz)
     dev = dz.device
     pick = lambda t: t if t is not None else _empty(dev)
