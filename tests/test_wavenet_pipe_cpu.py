@@ -4,7 +4,7 @@ stage's lanes do with the images (register image: wave, register index, lane; LD
 import numpy as np
 import torch
 
-from viai_amd import wavenet as WN
+from viai_amd import wavenet_synth as WN
 
 NL, NCU, NW, GW, BW, C, H, S, CIN = 24, 10, 8, 7, 10, 512, 256, 256, 80
 R5 = np.float64(0.5) ** 0.5

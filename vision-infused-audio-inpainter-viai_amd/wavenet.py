@@ -13,7 +13,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, ops, wavenet_synth
 from .ops import ACT_NONE, ACT_RELU, _c, _ptr, _require, _stream
 
 
@@ -235,6 +235,15 @@ class _Upsample(torch.autograd.Function):
         return dx, dw, db
 
 
+def _scale_saved_grad(ctx, g):
+    """backward of the two fused losses: the forward pass left d loss / d yhat on ctx, the incoming scalar gradient scales it in place"""
+    lib = _lib.load()
+    d = ctx.dyh
+    g = _c(g)
+    _lib.check(lib.viai_scale_by_scalar(d.data_ptr(), g.data_ptr(), d.numel(), _stream()), "viai_scale_by_scalar")
+    return d, None, None, None, None
+
+
 class _MoLLoss(torch.autograd.Function):
     """DiscretizedMixturelogisticLoss: masked mean of the MoL negative log-likelihood (loss_functions.py:43-62)."""
 
@@ -259,11 +268,7 @@ class _MoLLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, _g2):
-        lib = _lib.load()
-        d = ctx.dyh
-        g = _c(g)
-        _lib.check(lib.viai_scale_by_scalar(d.data_ptr(), g.data_ptr(), d.numel(), _stream()), "viai_scale_by_scalar")
-        return d, None, None, None, None
+        return _scale_saved_grad(ctx, g)
 
 
 def mol_loss(yhat_nhwc, y, mask=None, num_classes=65536, log_scale_min=math.log(1e-14)):
@@ -318,11 +323,7 @@ class _MaskedCE(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, _g2):
-        lib = _lib.load()
-        d = ctx.dyh
-        g = _c(g)
-        _lib.check(lib.viai_scale_by_scalar(d.data_ptr(), g.data_ptr(), d.numel(), _stream()), "viai_scale_by_scalar")
-        return d, None, None, None, None
+        return _scale_saved_grad(ctx, g)
 
 
 def masked_cross_entropy(yhat_nhwc, target, mask=None, shift=0, num_classes=None):
@@ -409,8 +410,7 @@ def mulaw_decode(classes, mu=255):
     lib = _lib.load()
     k = classes.to(torch.int32).contiguous()
     out = torch.empty(k.shape, dtype=torch.float32, device=k.device)
-    _lib.check(lib.viai_mulaw_decode(k.data_ptr(), out.data_ptr(), k.numel(), int(mu), torch.cuda.current_stream().cuda_stream),
-               "viai_mulaw_decode")
+    _lib.check(lib.viai_mulaw_decode(k.data_ptr(), out.data_ptr(), k.numel(), int(mu), _stream()), "viai_mulaw_decode")
     return out
 
 
@@ -421,8 +421,7 @@ def mulaw_quantize(x, mu=255):
     lib = _lib.load()
     xx = x.to(torch.float32).contiguous()
     out = torch.empty(xx.shape, dtype=torch.int32, device=xx.device)
-    _lib.check(lib.viai_mulaw_quantize(xx.data_ptr(), out.data_ptr(), xx.numel(), int(mu), torch.cuda.current_stream().cuda_stream),
-               "viai_mulaw_quantize")
+    _lib.check(lib.viai_mulaw_quantize(xx.data_ptr(), out.data_ptr(), xx.numel(), int(mu), _stream()), "viai_mulaw_quantize")
     return out.long()
 
 
@@ -452,53 +451,6 @@ def conv1d_apply(x, m, act=ACT_NONE, causal_crop=False):
     k, d, p = m.kernel_size[0], m.dilation[0], m.padding[0]
     return ops.conv_bn_act(x, w, m.bias, None, kernel=(1, k), stride=(1, 1), padding=(0, p), dilation=(1, d),
                            padding2=(-1, 0 if causal_crop else -1), act=act)
-
-
-def _pipe_images(w_stage, b_stage, w_c, w_out, b_out, w_skip, b_skip, w_l1, b_l1, w_l2, b_l2, dev):
-    """Weight images of the pipelined synthesis kernel (csrc/wavenet_pipe.hip; layouts in include/viai_hip.h, viai_wn_pipe_image_floats).
-    Inputs: per layer the fused gate rows `w_stage[l]` [G][3C (+H for l > 0)] / `b_stage[l]` [G] of the chain form, the conditioning rows `w_c[l]`
-    [G][cin], and the out / skip 1x1s; the head's two 1x1s.  Compute unit j of layer l owns gate pairs h in [26 j, 26 j + 26), residual rows
-    [52 j, 52 j + 52) and skip rows [26 j, 26 j + 26) -- row SLOTS beyond a range are zero rows.  Pure re-arrangement: no arithmetic on the weights."""
-    NL, NCU, NW, GW, BW, C, H, S = 24, 10, 8, 7, 10, 512, 256, 256
-    G = 2 * H
-    j = torch.arange(NCU).view(NCU, 1)
-    r = torch.arange(NW * GW).view(1, -1)
-    hh = 26 * j + torch.where(r < 26, r, r - 26)
-    grow = torch.where((r < 52) & (hh < H), hh + torch.where(r < 26, 0, H), torch.full_like(hh, G)).to(dev)          # [10][56] -> gate row, G = the zero row
-    q = torch.arange(NW * BW).view(1, -1)
-    xrow = 52 * j + q
-    srow = 26 * j + (q - 52)
-    # B slots: < 52 residual row, 52 .. 77 skip row (offset C in the stacked [Wo; Ws] matrix), C + S = the zero row
-    brow = torch.where((q < 52) & (xrow < C), xrow, torch.where((q >= 52) & (q < 78) & (srow < S), C + srow, torch.full_like(xrow, C + S))).to(dev)
-    wreg, wcond, wlds, bias = [], [], [], []
-    z1 = lambda n: torch.zeros(1, n, device=dev)
-    for l in range(NL):
-        ws = w_stage[l]
-        if ws.size(1) == 3 * C:
-            ws = torch.cat((ws, torch.zeros(G, H, device=dev)), 1)                      # layer 0: no z columns
-        W = torch.cat((ws, z1(3 * C + H)), 0)[grow]                                     # [10][56][1792]
-        # register image: wave = 128 past-tap / 64 current-tap columns of all 52 rows; lane (g, cg) = (lane / 16, lane % 16) holds rows 13 g + i (i < 13):
-        # register 8 i + 4 m + e = past-tap column 128 wave + 64 m + 4 cg + e, register 104 + 4 i + e = current-tap column 64 wave + 4 cg + e
-        pre = W[:, :52, :2 * C].reshape(NCU, 4, 13, NW, 2, 16, 4).permute(0, 3, 2, 4, 6, 1, 5).reshape(NCU, NW, 104, 64)
-        cur = W[:, :52, 2 * C:3 * C].reshape(NCU, 4, 13, NW, 16, 4).permute(0, 3, 2, 5, 1, 4).reshape(NCU, NW, 52, 64)
-        wreg.append(torch.cat((pre, cur), 2))                                           # 104 + 52 registers
-        wc = torch.cat((w_c[l], z1(w_c[l].size(1))), 0)[grow]                           # [10][56][80]
-        wcond.append(torch.cat((wc, torch.zeros(NCU, 8, wc.size(2), device=dev)), 1))   # 64 row slots
-        bg = torch.cat((b_stage[l], torch.zeros(1, device=dev)))[grow]                  # [10][56]
-        if l == 0:
-            wB, bB = torch.zeros(NCU, NW * BW, H, device=dev), torch.zeros(NCU, NW * BW, device=dev)
-        else:
-            wB = torch.cat((w_out[l - 1], w_skip[l - 1], z1(H)), 0)[brow]               # [10][80][256]
-            bB = torch.cat((b_out[l - 1], b_skip[l - 1], torch.zeros(1, device=dev)))[brow]
-        rows = torch.cat((W[:, :52, 3 * C:], wB[:, :78]), 1)                            # LDS rows: 52 gate rows (z columns), 78 out / skip rows
-        wlds.append(torch.nn.functional.pad(rows, (0, 4)))                              # rows padded to 260 floats (lane = row reads without bank conflicts)
-        bias.append(torch.cat((bg, bB), 1))
-    head_w = torch.cat((w_skip[NL - 1], w_l1, w_l2, torch.zeros(32 - w_l2.size(0), S, device=dev)), 0)
-    head_b = torch.cat((b_skip[NL - 1], b_l1, b_l2, torch.zeros(32 - b_l2.numel(), device=dev)))
-    c = lambda ts: torch.stack(ts).float().contiguous()
-    return c(wreg), c(wcond), c(wlds), c(bias), head_w.float().contiguous(), head_b.float().contiguous()
-
-
 
 class ResidualConv1dGLU(nn.Module):
     """modules.py:84-216."""
@@ -574,7 +526,7 @@ class WaveNet(nn.Module):
                 m.bias.data.zero_()
                 self.upsample_conv.append(_wn(m, weight_normalization))
                 self.upsample_conv.append(nn.ReLU(inplace=True))
-        self.receptive_field = (kernel_size - 1) * sum(2 ** (i % per) for i in range(layers)) + 1
+        self.receptive_field = receptive_field_size(layers, stacks, kernel_size)
 
     def seed_dropout(self, seed, calls=0):
         """Fix the dropout masks of training: forward number n (counted from `calls`) of layer l drops by (seed, offset = n * 1024 + l).
@@ -688,215 +640,8 @@ class WaveNet(nn.Module):
         `uniforms=(u1 (B,T,10), u2 (B,T))` injects the sampler's two uniform draws (parity tests); default torch.rand.
         `timing={"warmup": W}` (bench.py): the first W time steps run untimed, the remaining T - W are bracketed by device
         synchronisations and reported as timing["ms"] / timing["steps"] (set-up -- weight norm, linearised weights -- excluded)."""
-        import ctypes as Ct
-        cat = not self.scalar_input
-        K = self.out_channels
-        if cat:
-            if quantize and not softmax:
-                raise ValueError("incremental_forward: quantize=True needs softmax=True (logits are no probabilities to draw a class from)")
-            if return_logits:
-                raise ValueError("incremental_forward: return_logits belongs to the mixture-of-logistics network; softmax=False, quantize=False returns the logits")
-            if return_classes and not quantize:
-                raise ValueError("incremental_forward: return_classes needs quantize=True")
-            if input_form not in ("auto", "dense"):
-                raise ValueError("incremental_forward: input_form is 'auto' or 'dense'")
-        lib = _lib.load()
-        dev = self.first_conv.bias.device
-        tcls = init_rows = None
-        if test_inputs is not None:
-            if test_inputs.size(1) == (K if cat else 1):
-                test_inputs = test_inputs.transpose(1, 2)                             # -> (B, n, K) / (B, n, 1)  (wavenet.py:268-274)
-            B = test_inputs.size(0)
-            T = test_inputs.size(1) if T is None else max(int(T), test_inputs.size(1))
-            if cat:
-                tin = test_inputs.to(dev).float().contiguous()                        # (B, n, K)
-                assert tin.size(2) == K, "test_inputs: (B, K, n) or (B, n, K)"
-                if input_form == "auto" and bool((((tin == 0) | (tin == 1)).all(-1) & (tin.sum(-1) == 1)).all()):
-                    tcls = tin.argmax(-1).to(torch.int32).contiguous()                # exactly one-hot rows: the class form
-            else:
-                tin = test_inputs.reshape(B, -1).to(dev).float().contiguous()
-        else:
-            B = c.size(0) if c is not None else (initial_input.size(0) if (cat and initial_input is not None) else 1)
-            tin = None
-        T = int(T)
-        if cat and initial_input is None and tin is None and K <= 127:
-            raise ValueError("incremental_forward: the default initial input is class 127 (wavenet.py:308-312); with %d classes pass initial_input" % K)
-        if cat and initial_input is not None:                                         # wavenet.py:316-318
-            if initial_input.size(1) == K:
-                initial_input = initial_input.transpose(1, 2)
-            init_rows = initial_input.to(dev).float().reshape(B, K).contiguous()
-        if not 1 <= B <= 32:
-            raise NotImplementedError("incremental_forward: 1 to 32 streams")
-        cond = None
-        if c is not None:
-            cu = self._upsample(c.to(dev).float())
-            assert cu.size(-1) == T
-            cond = cu.transpose(1, 2).contiguous()                                    # (B, T, cin)
-        if cat:
-            u1 = None
-            u2 = torch.rand(B, T, device=dev) if uniforms is None else uniforms.to(dev).float().reshape(B, T).contiguous()
-        elif uniforms is None:
-            u1 = torch.empty(B, T, self.out_channels // 3, device=dev).uniform_(1e-5, 1.0 - 1e-5)
-            u2 = torch.empty(B, T, device=dev).uniform_(1e-5, 1.0 - 1e-5)
-        else:
-            u1, u2 = uniforms[0].to(dev).float().contiguous(), uniforms[1].to(dev).float().contiguous()
-        g_vec = None
-        if g is not None:                                                            # wavenet.py:284-290: time-invariant
-            g = g.to(dev)
-            g_vec = (self.embed_speakers(g.view(B, -1)).transpose(1, 2) if self.embed_speakers is not None else g.float().view(B, -1, 1)).contiguous()
-        Cc = self.first_conv.bias.numel()
-        f0 = self.conv_layers[0]
-        G, S = f0.conv.bias.numel(), f0.conv1x1_skip.bias.numel()
-        keep = []                                                                     # keep tensors alive
-
-        def t(x):
-            x = x.detach().float().contiguous()
-            keep.append(x)
-            return x.data_ptr()
-        layers = (_lib.WnLayer * len(self.conv_layers))()
-        held = {k: [] for k in ("w_stage", "b_stage", "w_c", "w_out", "b_out", "w_skip", "b_skip")}         # the tensors behind the pointers (pipelined form)
-
-        def th(key, x):
-            x = x.detach().float().contiguous()
-            keep.append(x)
-            held[key].append(x)
-            return x.data_ptr()
-        # fused stages (csrc/wavenet.hip, ABI 7): gate_l from z_{l-1} and x_{l-1}(t) through the extended rows built below -- one
-        # dependent launch per layer instead of two
-        import os
-        fuse = os.environ.get("VIAI_WN_FUSED", "1") != "0" and S <= 256 and self.out_channels <= 256 and G // 2 <= 256
-        r5 = math.sqrt(0.5)
-        prev = None
-        for i, f in enumerate(self.conv_layers):
-            d = f.conv.dilation[0]
-            ring = torch.zeros(B, 2 * d + 1, Cc, device=dev)
-            keep.append(ring)
-            L = layers[i]
-            L.w_conv = t(normed_weight(f.conv).permute(0, 2, 1).reshape(G, -1))       # linearised (conv.py:53-57)
-            L.b_conv = t(f.conv.bias)
-            L.w_c = th("w_c", normed_weight(f.conv1x1c).reshape(G, -1)) if (f.conv1x1c is not None and cond is not None) else None
-            L.b_c = t(f.conv1x1c.bias) if (f.conv1x1c is not None and cond is not None) else None
-            L.w_out, L.b_out = th("w_out", normed_weight(f.conv1x1_out).reshape(Cc, -1)), th("b_out", f.conv1x1_out.bias)
-            L.w_skip, L.b_skip = th("w_skip", normed_weight(f.conv1x1_skip).reshape(S, -1)), th("b_skip", f.conv1x1_skip.bias)
-            L.ring, L.dilation, L.ring_len = ring.data_ptr(), d, 2 * d + 1
-            if fuse:
-                # (set-up arithmetic, once per synthesis call, in fp64 on the host: no library GEMM on the device path)
-                wlin = normed_weight(f.conv).permute(0, 2, 1).reshape(G, -1).double().cpu()     # [Wc^0 | Wc^1 | Wc^2]
-                bias = f.conv.bias.double().cpu()
-                if f.conv1x1c is not None and cond is not None:
-                    bias = bias + f.conv1x1c.bias.double().cpu()
-                if prev is not None:
-                    wc2 = wlin[:, 2 * Cc:]
-                    wo, bo = normed_weight(prev.conv1x1_out).reshape(Cc, -1).double().cpu(), prev.conv1x1_out.bias.double().cpu()
-                    wlin = torch.cat((wlin[:, :2 * Cc], r5 * wc2, r5 * (wc2 @ wo)), 1)
-                    bias = bias + r5 * (wc2 @ bo)
-                L.w_stage, L.b_stage = th("w_stage", wlin.float().to(dev)), th("b_stage", bias.float().to(dev))
-                prev = f
-            # global conditioning adds conv1x1g(g) + bias to the gate pre-activation at every step (modules.py:195-199):
-            # computed once per layer by the HIP 1x1 conv and handed to the step kernel as a per-stream constant
-            L.g_add = (t(conv1d_apply(g_vec.transpose(1, 2).reshape(B, 1, 1, -1).contiguous(), f.conv1x1g).reshape(B, G))
-                       if (g_vec is not None and f.conv1x1g is not None) else None)
-        # categorical network: `out` is the head's scratch (hidden layer, logits), `logits` the (B, T, K) rows of the reference's `outputs`
-        out = torch.zeros(B, S + K, device=dev) if cat else torch.zeros(B, T, device=dev)
-        logits = torch.zeros(B, T, self.out_channels, device=dev) if (return_logits or (cat and not return_classes)) else None
-        classes = torch.zeros(B, T, dtype=torch.int32, device=dev) if cat else None
-        z = torch.zeros(B, G // 2, device=dev)
-        z2 = torch.zeros(B, G // 2, device=dev)
-        skips = torch.zeros(B, S, device=dev)
-        step = torch.zeros(1, dtype=torch.int32, device=dev)        # time index, advanced on the device by each step
-        st = _lib.WnSynth()
-        st.B, st.C, st.G, st.S, st.cin, st.n_layers, st.out_ch, st.T = B, Cc, G, S, (cond.size(2) if cond is not None else 4), len(self.conv_layers), self.out_channels, T
-        st.n_test = tin.size(1) if tin is not None else 0
-        st.log_scale_min = float(log_scale_min)
-        st.layers = layers
-        st.w_first, st.b_first = t(normed_weight(self.first_conv).reshape(-1)), t(self.first_conv.bias)      # categorical: [C][K]
-        if cat:
-            st.categorical, st.cat_softmax, st.cat_quantize, st.init_class = 1, int(bool(softmax)), int(bool(quantize)), 127 if K > 127 else 0
-            st.w_first_t = t(normed_weight(self.first_conv).reshape(Cc, K).t())                              # [K][C]: a class is one row
-            st.test_classes = tcls.data_ptr() if tcls is not None else None
-            st.init_rows = init_rows.data_ptr() if init_rows is not None else None
-            st.classes = classes.data_ptr()
-        st.w_l1, st.b_l1 = t(normed_weight(self.last_conv_layers[1]).reshape(S, -1)), t(self.last_conv_layers[1].bias)
-        st.w_l2, st.b_l2 = t(normed_weight(self.last_conv_layers[3]).reshape(self.out_channels, -1)), t(self.last_conv_layers[3].bias)
-        st.cond = cond.data_ptr() if cond is not None else None
-        st.test_inputs = tin.data_ptr() if tin is not None else None
-        st.u1, st.u2, st.out, st.z, st.skips, st.step = (u1.data_ptr() if u1 is not None else None), u2.data_ptr(), out.data_ptr(), z.data_ptr(), skips.data_ptr(), step.data_ptr()
-        st.yhat_dbg = logits.data_ptr() if logits is not None else None
-        st.z2, st.fused = z2.data_ptr(), 1 if fuse else 0
-        ref = Ct.byref(st)
-        # the pipelined form (csrc/wavenet_pipe.hip): one persistent launch, the stages work on different streams at the same time.  Reference-size
-        # network with local conditioning only; everything else (and use_graph) takes the chain of launches below.
-        pipe = (not use_graph) and fuse and os.environ.get("VIAI_WN_PIPE", "1") != "0" and bool(lib.viai_wn_pipe_ok(ref))
-        if not pipe and B not in (1, 2, 4, 8):
-            raise NotImplementedError("incremental_forward: the chain of launches takes 1, 2, 4 or 8 streams; any other count up to 32 needs the pipelined form "
-                                      "(reference-size network, local conditioning only, no use_graph, VIAI_WN_PIPE != 0, a device with 256 compute units)")
-        if cat and not lib.viai_wn_categorical_ok(ref):
-            raise NotImplementedError("incremental_forward: the one-hot network needs out_channels <= 256 and a multiple of 4, channel counts that are multiples of 4")
-        if pipe:
-            imgs = _pipe_images(held["w_stage"], held["b_stage"], held["w_c"], held["w_out"], held["b_out"], held["w_skip"], held["b_skip"],
-                                normed_weight(self.last_conv_layers[1]).reshape(S, -1).detach().float(), self.last_conv_layers[1].bias.detach().float(),
-                                normed_weight(self.last_conv_layers[3]).reshape(self.out_channels, -1).detach().float(), self.last_conv_layers[3].bias.detach().float(), dev)
-            for k, im in enumerate((imgs[0], imgs[2], imgs[3], imgs[4], imgs[5], imgs[1])):
-                assert im.numel() == lib.viai_wn_pipe_image_floats(k), (k, im.numel(), lib.viai_wn_pipe_image_floats(k))
-            dil = (Ct.c_int * len(self.conv_layers))(*[f.conv.dilation[0] for f in self.conv_layers])
-            tok = torch.zeros(lib.viai_wn_pipe_token_granules(B, dil), dtype=torch.int64, device=dev)
-            err = torch.zeros(4, dtype=torch.int32, device=dev)
-            w0 = min(int(timing.get("warmup", 0)), T) if timing is not None else 0
-
-            def run(t0, n):
-                _lib.check(lib.viai_wn_pipe_run(ref, imgs[0].data_ptr(), imgs[1].data_ptr(), imgs[2].data_ptr(), imgs[3].data_ptr(), imgs[4].data_ptr(), imgs[5].data_ptr(),
-                                                tok.data_ptr(), err.data_ptr(), t0, n, torch.cuda.current_stream().cuda_stream), "viai_wn_pipe_run")
-            if w0 > 0:
-                run(0, w0)
-            if timing is not None:
-                import time
-                torch.cuda.synchronize()
-                t_start = time.perf_counter()
-            for t0 in tqdm(range(w0, T, 1024)):
-                run(t0, min(1024, T - t0))
-            if timing is not None:
-                torch.cuda.synchronize()
-                timing["ms"], timing["steps"], timing["form"] = (time.perf_counter() - t_start) * 1e3, T - w0, "pipe"
-            e = err.tolist()
-            if e[0] != 0:
-                raise _lib.ViaiLibraryError("viai_wn_pipe_run failed on the device: %s at stage %d, stream %d, t = %d (the pipelined form needs all of its 249 blocks "
-                                            "resident at once, i.e. the whole chip to itself; VIAI_WN_PIPE=0 selects the chain of launches)"
-                                            % ("a wait timed out" if e[0] == 1 else "a past tap was missing", e[1], e[2], e[3]))
-        elif use_graph and T > 2:
-            # device-side time index: one step captured into a HIP graph and replayed (every kernel starts with a load of the index)
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                _lib.check(lib.viai_wavenet_synth_step(ref, torch.cuda.current_stream().cuda_stream), "viai_wavenet_synth_step")   # step 0 (warm-up)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                _lib.check(lib.viai_wavenet_synth_step(ref, torch.cuda.current_stream().cuda_stream), "viai_wavenet_synth_step")   # captured: step 1
-            for _ in tqdm(range(T - 1)):
-                graph.replay()
-        else:
-            # default: the C side loops over the time steps and hands every kernel its time index by value
-            chunk = 64
-            w0 = min(int(timing.get("warmup", 0)), T) if timing is not None else 0
-            if w0 > 0:
-                _lib.check(lib.viai_wavenet_synth_run(ref, 0, w0, torch.cuda.current_stream().cuda_stream), "viai_wavenet_synth_run")
-            if timing is not None:
-                import time
-                torch.cuda.synchronize()
-                t_start = time.perf_counter()
-            for t0 in tqdm(range(w0, T, chunk)):
-                _lib.check(lib.viai_wavenet_synth_run(ref, t0, min(chunk, T - t0), torch.cuda.current_stream().cuda_stream), "viai_wavenet_synth_run")
-            if timing is not None:
-                torch.cuda.synchronize()
-                timing["ms"], timing["steps"] = (time.perf_counter() - t_start) * 1e3, T - w0
-        torch.cuda.current_stream().synchronize()
-        del keep
-        if cat:
-            if return_classes:
-                return classes.long()
-            return logits.transpose(1, 2).contiguous()                                # (B, K, T) like the reference (wavenet.py:358-361)
-        res = out.unsqueeze(1)                                                        # (B, 1, T) like the reference
-        return (res, logits) if return_logits else res
+        return wavenet_synth.incremental_forward(self, initial_input, c, g, T, test_inputs, tqdm, softmax, quantize, log_scale_min, uniforms, use_graph,
+                                                 return_logits, timing, return_classes, input_form)
 
     def make_generation_fast_(self):
         def rm(m):
