@@ -92,11 +92,9 @@ def conv_takes_p16(x_shape, weight, kernel, stride, padding, transposed):
     (what a producer asks before it writes its output as P16: networks.py)"""
     if not P16:
         return False
-    N, IH, IW, C1 = x_shape
-    Cout = weight.shape[1] if transposed else weight.shape[0]
-    if C1 % 32 != 0:
+    if x_shape[3] % 32 != 0:
         return False
-    d = conv_desc(N, IH, IW, C1, 0, Cout, kernel[0], kernel[1], stride[0], stride[1], padding[0], padding[1], 1 if transposed else 0)
+    d = _layer_desc(x_shape, 0, weight, kernel, stride, padding, transposed)
     return (p16_mask(d) & (P16_OK_FWD_X | P16_OK_WGRAD_X)) == (P16_OK_FWD_X | P16_OK_WGRAD_X)
 
 
@@ -104,12 +102,9 @@ def conv_wgrad_takes_p16(x_shape, weight, kernel, stride, padding, transposed):
     """... or at least in its weight-gradient kernel?  (a residual join then still writes the twin: the forward of such a layer reads the fp32 tensor)"""
     if not (P16 and F16_BACKWARD):
         return False
-    N, IH, IW, C1 = x_shape
-    Cout = weight.shape[1] if transposed else weight.shape[0]
-    if C1 % 32 != 0:
+    if x_shape[3] % 32 != 0:
         return False
-    d = conv_desc(N, IH, IW, C1, 0, Cout, kernel[0], kernel[1], stride[0], stride[1], padding[0], padding[1], 1 if transposed else 0)
-    caps = _caps(d)
+    caps = _caps(_layer_desc(x_shape, 0, weight, kernel, stride, padding, transposed))
     return bool(caps.p16 & P16_OK_WGRAD_X) and caps.wgrad_f16
 
 
@@ -482,6 +477,16 @@ def conv_desc(N, IH, IW, C1, C2, Cout, kh, kw, sh, sw, ph, pw, transposed, dh=1,
     return d
 
 
+def _layer_desc(x_shape, C2, weight, k, s, p, transposed, d=(1, 1), p2=(-1, -1)):
+    """descriptor of the conv of a fused layer: an NHWC input of x_shape (beside C2 channels of a second source), weight in the torch layout
+    of nn.Conv2d / nn.ConvTranspose2d, the geometry as _LayerSpec holds it.  The one place that reads Cout / Cin off the weight."""
+    N, IH, IW, C1 = x_shape
+    Cout, cin_w = (weight.shape[1], weight.shape[0]) if transposed else (weight.shape[0], weight.shape[1])
+    if C2 == 0 and C1 == 4 and 1 < cin_w < 4:
+        C1 = cin_w                      # frames stored with channel stride 4 (zero padded): ResNet conv1
+    return conv_desc(N, IH, IW, C1, C2, Cout, k[0], k[1], s[0], s[1], p[0], p[1], 1 if transposed else 0, d[0], d[1], p2[0], p2[1])
+
+
 def _wgrad_side(trail, st):
     """where a weight-gradient launch goes: (stream object for _scratch, raw handle).  With `trail` and a WGRAD_STREAM, the side stream,
     ordered behind what the current stream has queued so far -- the caller then keeps the launch's operands alive in _deferred; otherwise (None, st).
@@ -527,14 +532,14 @@ def _wgrad_call(lib, d, x, x2, dy, ws, dw, db, acc, amax, xa, flags, handle):
                    "viai_conv2d_wgrad")
 
 
-def _conv_grads(lib, d, cfg, dims, has_bn, has_bias, needs, xa, x, x2, weight, dy, amax, st, dy_p16=False, x_p16=False, dy_w=None):
+def _conv_grads(lib, d, spec, dims, has_bn, has_bias, needs, xa, x, x2, weight, dy, amax, st, dy_p16=False, x_p16=False, dy_w=None):
     """weight / bias / data gradients of one conv layer from dy (the gradient of its output): the tail every fused layer's backward
     shares.  needs = (need_x, need_x2, need_w, need_b); returns (dx, dx2, dw, db) with None where the gradient went into the arena."""
     N, IH, IW, C1, C2, Cout, OH, OW = dims
     M = N * OH * OW
     dev = dy.device
     need_x, need_x2, need_w, need_b = needs
-    gt = cfg.get("gt") or (None, None, None, None)
+    gt = spec.gt
     dw = db = dx = dx2 = None
     caps = _caps(d)
     if need_w and x_p16 and not (caps.p16 & P16_OK_WGRAD_X and (amax is not None and caps.wgrad_f16)):
@@ -545,7 +550,7 @@ def _conv_grads(lib, d, cfg, dims, has_bn, has_bias, needs, xa, x, x2, weight, d
     flags = (1 if (dy_p16 or dy_w is not None) else 0) | (2 if x_p16 else 0)
     if need_w or (need_b and has_bias):
         ws = None
-        shadowed = has_bn and cfg["training"]     # bias in front of train-mode BN: gradient is exactly 0
+        shadowed = has_bn and spec.training     # bias in front of train-mode BN: gradient is exactly 0
         acc_w = gt[0] is not None and need_w
         dw = gt[0] if acc_w else torch.empty_like(weight)
         acc_b = False
@@ -625,7 +630,7 @@ def _dy_form(caps, need_x, need_w, need_b, act, tail, has_bias, training, Cout, 
     return want_amax, DY_TWIN if (need_x and need_w and w_planes) else DY_PLAIN
 
 
-def _stage_input(d, caps, x, x2, xp, cfg, st):
+def _stage_input(d, caps, x, x2, xp, xa_in, st):
     """the conv's input as its forward kernel takes it: (x, x is pre-split, operand magnitude or None).  A pre-split x the layer has no loader
     for is decoded (the networks of this package ask conv_takes_p16 first); the planes carry the scale they were written with; an fp32 input
     of an f16x2 kernel gets its magnitude from the tensors' provenance or one absmax pass."""
@@ -633,7 +638,7 @@ def _stage_input(d, caps, x, x2, xp, cfg, st):
         x, xp = p16_decode(x), False
     if xp:
         return x, True, amax_of(x)
-    return x, False, (_input_amax(x, x2, cfg.get("xa_in", (None, None)), st) if (caps.fwd_f16 and F16_DYNAMIC) else None)
+    return x, False, (_input_amax(x, x2, xa_in, st) if (caps.fwd_f16 and F16_DYNAMIC) else None)
 
 
 def _conv_fwd(lib, d, x, x2, xp, xa, wp, bias, out, stat, act, st):
@@ -644,34 +649,35 @@ def _conv_fwd(lib, d, x, x2, xp, xa, wp, bias, out, stat, act, st):
                    "viai_conv2d_fwd")
 
 
-def _conv_bn_coef(lib, d, caps, x, x2, xp, xa, wp, bias, bn, cfg, y, coef, st):
+def _conv_bn_coef(lib, d, caps, x, x2, xp, xa, wp, bias, bn, spec, y, coef, st):
     """y = conv(x ++ x2) + bias and the BatchNorm coefficients (mean, invstd, scale, shift) behind it: from the batch statistics the conv kernel
     leaves as partials (training; updates the running statistics) or from the running statistics (eval)"""
     gamma, beta, rmean, rvar, nbt = bn
     Cc = coef.shape[1]
-    if cfg["training"]:
+    if spec.training:
         stat = _scratch("stat", 2 * Cc * d["nblk"], y.device)
         _conv_fwd(lib, d, x, x2, xp, xa, wp, bias, y, stat.data_ptr(), ACT_NONE, st)
-        _bn_finalize(lib, d, stat, y.numel() // Cc, Cc, gamma, beta, rmean, rvar, nbt, cfg, coef, st, lin=xp and bool(caps.p16 & P16_OK_FWD_LIN))
+        _bn_finalize(lib, d, stat, y.numel() // Cc, Cc, gamma, beta, rmean, rvar, nbt, {"momentum": spec.momentum, "eps": spec.eps}, coef, st, lin=xp and bool(caps.p16 & P16_OK_FWD_LIN))
     else:
         _conv_fwd(lib, d, x, x2, xp, xa, wp, bias, y, 0, ACT_NONE, st)
-        _lib.check(lib.viai_bn_eval_coeffs(Cc, gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(), cfg["eps"], *_rows(coef), st),
+        _lib.check(lib.viai_bn_eval_coeffs(Cc, gamma.data_ptr(), beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(), spec.eps, *_rows(coef), st),
                    "viai_bn_eval_coeffs")
 
 
-# The BatchNorm-apply tails of _ConvBnAct.forward: z from the pre-BatchNorm map y in one pass, max |z| into za.  Each returns z and what the
-# backward needs beside (x, x2, weight, y, coef); a tail that also writes z as planes leaves them in cfg (z_p16: z itself; z_twin: a second tensor).
+# The BatchNorm-apply tails of _ConvBnAct.forward: z from the pre-BatchNorm map y in one pass, max |z| into za.  Each returns (z, what the backward
+# needs beside (x, x2, weight, y, coef), True where z itself holds planes -- None otherwise --, a second tensor that holds z as planes or None).
 # p16_out: the consumer stages pre-split pieces (networks.py asked conv_takes_p16) and the layer can write them (training, Cout % 32 == 0).
 
-def _tail_pool(lib, cfg, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
+def _tail_pool(lib, spec, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
     # BatchNorm + activation + max-pool: the post-activation map is never stored (the backward gathers its gradient from the pooled
     # gradient and the argmax bytes inside the BatchNorm-backward passes)
     N, OH, OW, Cout = dims
-    k_, s_, p_ = cfg["pool"]
+    k_, s_, p_ = spec.pool
     PH, PW = (OH + 2 * p_ - k_) // s_ + 1, (OW + 2 * p_ - k_) // s_ + 1
     sc, sh = _rows(coef)[2:]
     z = torch.empty((N, PH, PW, Cout), device=y.device, dtype=torch.float32)
     pidx = torch.empty((N, PH, PW, Cout), device=y.device, dtype=torch.uint8)
+    zp = None
     if p16_out and (k_, s_, p_) == (3, 2, 1) and z.numel() // 4 < (1 << 31) - (1 << 24):
         zp = torch.empty_like(z)
         pa = _amax_slot(y.device)
@@ -679,14 +685,13 @@ def _tail_pool(lib, cfg, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
                                                     pidx.data_ptr(), N, OH, OW, Cout, k_, s_, p_, act, 0.2, za.data_ptr(), pa.data_ptr(), st),
                    "viai_bn_act_maxpool_fwd_twin")
         zp._viai_p16, zp._viai_amax = True, pa
-        cfg["z_twin"] = zp
     else:
         _lib.check(lib.viai_bn_act_maxpool_fwd(y.data_ptr(), sc, sh, z.data_ptr(), pidx.data_ptr(), N, OH, OW, Cout, k_, s_, p_, act, 0.2, za.data_ptr(), st),
                    "viai_bn_act_maxpool_fwd")
-    return z, (pidx,)
+    return z, (pidx,), None, zp
 
 
-def _tail_res(lib, cfg, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
+def _tail_res(lib, spec, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
     # BatchNorm + residual add + activation (ResNet BasicBlock); z is kept: the activation's mask needs the sum
     N, OH, OW, Cout = dims
     M = N * OH * OW
@@ -695,6 +700,7 @@ def _tail_res(lib, cfg, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
     z = torch.empty_like(y)
     ra = amax_of(res)
     c4 = Cout // 4
+    zp = None
     if p16_out and ra is not None and c4 <= 256 and (c4 & (c4 - 1)) == 0:
         # the next block's conv1 stages pre-split pieces: the join writes z twice (fp32 for the next join and the mask, P16 for the convs)
         zp = torch.empty_like(y)
@@ -702,48 +708,92 @@ def _tail_res(lib, cfg, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
         _lib.check(lib.viai_bn_add_act_fwd_twin(y.data_ptr(), sc, sh, gamma.data_ptr(), beta.data_ptr(), M, res.data_ptr(), ra.data_ptr(), z.data_ptr(),
                                                 zp.data_ptr(), M, Cout, act, 0.2, za.data_ptr(), pa.data_ptr(), st), "viai_bn_add_act_fwd_twin")
         zp._viai_p16, zp._viai_amax = True, pa
-        cfg["z_twin"] = zp
     else:
         _lib.check(lib.viai_bn_add_act_fwd_amax(y.data_ptr(), sc, sh, res.data_ptr(), z.data_ptr(), M, Cout, act, 0.2, za.data_ptr(), st), "viai_bn_add_act_fwd")
-    return z, (z,)
+    return z, (z,), None, zp
 
 
-def _tail_up(lib, cfg, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
+def _tail_up(lib, spec, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
     # BatchNorm + activation + the F.interpolate behind the layer: the post-activation map is not stored (the backward gathers its
     # gradient with the resize's backward and goes on from y)
     N, OH, OW, Cout = dims
-    UH, UW = cfg["up"]
+    UH, UW = spec.up
     sc, sh = _rows(coef)[2:]
     z = torch.empty((N, UH, UW, Cout), device=y.device, dtype=torch.float32)
     if p16_out:
         _lib.check(lib.viai_bn_act_bilinear_fwd_p16(y.data_ptr(), sc, sh, gamma.data_ptr(), beta.data_ptr(), N * OH * OW, z.data_ptr(), N, OH, OW, UH, UW,
                                                     Cout, act, 0.2, za.data_ptr(), st), "viai_bn_act_bilinear_fwd_p16")
-        cfg["z_p16"] = True
     else:
         _lib.check(lib.viai_bn_act_bilinear_fwd_amax(y.data_ptr(), sc, sh, z.data_ptr(), N, OH, OW, UH, UW, Cout, act, 0.2, za.data_ptr(), st),
                    "viai_bn_act_bilinear_fwd")
-    return z, ()
+    return z, (), p16_out or None, None
 
 
-def _tail_none(lib, cfg, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
+def _tail_none(lib, spec, y, coef, gamma, beta, res, dims, act, p16_out, za, st):
     N, OH, OW, Cout = dims
     M = N * OH * OW
     sc, sh = _rows(coef)[2:]
     z = torch.empty_like(y)
-    if p16_out and act in (ACT_NONE, ACT_RELU, ACT_LRELU):
+    planes = (p16_out and act in (ACT_NONE, ACT_RELU, ACT_LRELU)) or None
+    if planes:
         # z is written as the two fp16 planes, scale from the bound
         _lib.check(lib.viai_bn_act_fwd_p16(y.data_ptr(), sc, sh, gamma.data_ptr(), beta.data_ptr(), M, z.data_ptr(), M, Cout, act, 0.2, za.data_ptr(), st),
                    "viai_bn_act_fwd_p16")
-        cfg["z_p16"] = True
     else:
         _lib.check(lib.viai_bn_act_fwd_amax(y.data_ptr(), sc, sh, z.data_ptr(), M, Cout, act, 0.2, za.data_ptr(), st), "viai_bn_act_fwd")
-    return z, ()
+    return z, (), planes, None
 
 
 _TAILS = {"pool": _tail_pool, "res": _tail_res, "up": _tail_up, None: _tail_none}
 
-# what _ConvBnAct.backward needs of its forward beside the saved tensors (ctx.state; torch_ops.py builds one for its stand-in context)
-_LayerState = collections.namedtuple("_LayerState", "d cfg has_bn has_bias dims xa fused1 tail x_p16 x_twin_w xmask", defaults=(None, False, None, False, None, None))
+# One fused layer's configuration, as _layer_spec resolved it: forward and backward read it and never write it.  k s p d p2: kernel, stride,
+# padding, dilation, (bottom, right) padding; training: the BatchNorm normalises with batch statistics; xa_in: the magnitudes the inputs carried;
+# gt / gt2: DIRECT_GRAD targets of (weight, bias, gamma, beta) / the pair's (weight2, bias2), None where autograd gets the gradient.
+_LayerSpec = collections.namedtuple("_LayerSpec", "k s p transposed d p2 act training momentum eps pool up p16_out xmask xa_in gt transposed2 act2 gt2")
+
+# what a fused layer's backward needs of its forward beside the saved tensors (ctx.state; torch_ops.py builds one for its stand-in context);
+# d2 / has_bias2: the one-channel conv of the pair
+_LayerState = collections.namedtuple("_LayerState", "d spec has_bn has_bias dims xa fused1 tail x_p16 x_twin_w d2 has_bias2", defaults=(None, False, None, False, None, None, False))
+
+_Z_TAGS = ("_viai_amax", "_viai_p16", "_viai_twin")     # what conv_bn_act leaves on its output for the next layer
+
+
+class _LayerOut:
+    """what _ConvBnAct.forward hands its caller beside z, in the order of _Z_TAGS: max |z|, True where z holds planes, z once more as planes"""
+    __slots__ = ("za", "z_p16", "z_twin")
+
+    def __init__(self):
+        self.za = self.z_p16 = self.z_twin = None
+
+
+def _grad_target(p):
+    """the arena view that parameter p's gradient is accumulated into under DIRECT_GRAD, or None: autograd gets the gradient"""
+    return p.grad if (p is not None and p.is_leaf and p.requires_grad and p.grad is not None) else None
+
+
+def _layer_spec(params, bn, *, kernel, stride, padding, transposed, act, training, dilation=(1, 1), padding2=(-1, -1), xmask=None, pool=None, upsample=None,
+                out_p16=False, xa_in=(None, None), params2=(None, None), transposed2=False, act2=ACT_NONE, direct=None):
+    """(_LayerSpec, (gamma, beta, running_mean, running_var, num_batches_tracked) as the call passes them) of one fused layer.  params = (weight, bias),
+    params2 the pair's; bn: an nn.BatchNorm2d -- anything with its attributes -- or None; direct: take DIRECT_GRAD targets (default: the module switch).
+    A BatchNorm without running statistics normalises with batch statistics even in eval mode; the statistics are passed on where they are
+    tracked, the batch counter where they are updated.  (every tensor of the module is read once: a module attribute costs more than the rest of this)"""
+    training, momentum, eps, gamma, beta, stats = bool(training), 0.1, BN_EPS, None, None, (None, None, None)
+    if bn is not None:
+        gamma, beta = bn.weight, bn.bias
+        momentum, eps = 0.1 if bn.momentum is None else float(bn.momentum), float(bn.eps)
+        rmean = bn.running_mean if bn.track_running_stats else None
+        if rmean is not None:
+            stats = (rmean, bn.running_var, bn.num_batches_tracked if training else None)
+        else:
+            training = True
+    gt, gt2 = (None,) * 4, (None,) * 2
+    if DIRECT_GRAD if direct is None else direct:
+        gt = tuple(_grad_target(p) for p in (*params, gamma, beta))
+        gt2 = tuple(_grad_target(p) for p in params2)
+    return _LayerSpec(tuple(kernel), tuple(stride), tuple(padding), bool(transposed), tuple(dilation), tuple(padding2), int(act), training, momentum, eps,
+                      tuple(int(v) for v in pool) if pool is not None else None, (int(upsample[0]), int(upsample[1])) if upsample is not None else None,
+                      bool(out_p16) and gamma is not None and isinstance(bn, torch.nn.modules.batchnorm._BatchNorm), xmask, xa_in, gt,
+                      bool(transposed2), int(act2), gt2), (gamma, beta, *stats)
 
 
 class _ConvBnAct(torch.autograd.Function):
@@ -754,7 +804,8 @@ class _ConvBnAct(torch.autograd.Function):
     New_Inpainting_Networks.py:31-37,71-75,85-88, Discriminator_Networks.py:38-49)."""
 
     @staticmethod
-    def forward(ctx, x, x2, weight, bias, gamma, beta, rmean, rvar, nbt, res, cfg):
+    def forward(ctx, x, x2, weight, bias, gamma, beta, rmean, rvar, nbt, res, spec, twin, out):
+        # twin: a pre-split copy of x beside the fp32 tensor (the residual join of a ResNet block writes both); out: a _LayerOut to fill
         lib = _lib.load()
         xp = is_p16(x)
         _require(None if xp else x, x2, weight, bias, gamma, beta, res)
@@ -763,15 +814,8 @@ class _ConvBnAct(torch.autograd.Function):
         weight = _c(weight)
         N, IH, IW, C1 = x.shape
         C2 = x2.shape[3] if x2 is not None else 0
-        kh, kw = cfg["k"]
-        transposed = cfg["transposed"]
-        Cout = weight.shape[1] if transposed else weight.shape[0]
-        cin_w = weight.shape[0] if transposed else weight.shape[1]
-        if C2 == 0 and C1 == 4 and 1 < cin_w < 4:
-            C1 = cin_w                      # frames stored with channel stride 4 (zero padded): ResNet conv1
-        dil, p2 = cfg.get("d", (1, 1)), cfg.get("p2", (-1, -1))
-        d = conv_desc(N, IH, IW, C1, C2, Cout, kh, kw, cfg["s"][0], cfg["s"][1], cfg["p"][0], cfg["p"][1],
-                      1 if transposed else 0, dil[0], dil[1], p2[0], p2[1])
+        d = _layer_desc(x.shape, C2, weight, spec.k, spec.s, spec.p, spec.transposed, spec.d, spec.p2)
+        C1, Cout = d["desc"].C1, d["desc"].Cout
         caps = _caps(d)
         st = _stream()
         dev = x.device
@@ -781,9 +825,7 @@ class _ConvBnAct(torch.autograd.Function):
             _range_scan("weight", weight, F16_WEIGHT_LIMIT)
         wp = _packed(weight, d, 0, st)
         has_bn = gamma is not None
-        act = cfg["act"]
-        training = cfg["training"]
-        twin = cfg.pop("x_twin", None)          # a pre-split copy of x beside the fp32 tensor (the residual join of a ResNet block writes both)
+        act, training, xmask = spec.act, spec.training, spec.xmask
         # (both consumers of x must stage pieces: otherwise the weight gradient would decode the twin -- coarser scale -- although the exact fp32 x is at hand)
         x_twin_w = None
         if twin is not None and not xp and x2 is None and P16 and (caps.p16 & P16_OK_WGRAD_X) and F16_BACKWARD:
@@ -793,15 +835,14 @@ class _ConvBnAct(torch.autograd.Function):
                 # only the weight-gradient kernel stages pieces (the stride-2 3 x 3 convs of ResNet-18 on 28 / 14 / 7-pixel maps: their forward runs on the
                 # gather kernel): the forward reads the fp32 tensor, the weight gradient the planes -- it splits nothing (1143 -> ~650 us per launch)
                 x_twin_w = twin
-        x, xp, xa = _stage_input(d, caps, x, x2, xp, cfg, st)
+        # (the twin is an argument, not a field of the spec the state keeps: it lives on behind this forward only as x -- saved below -- or as x_twin_w)
+        x, xp, xa = _stage_input(d, caps, x, x2, xp, spec.xa_in, st)
         fused1 = has_bn and training and bias is None and C1 + C2 == 1 and caps.cin1_bn
-        xmask = cfg.get("xmask")
         if xmask is not None and not fused1:
             raise RuntimeError("conv_bn_act: xmask reached a layer that is not the fused Cin = 1 layer (conv_bn_act applies it up front otherwise)")
-        tail = "pool" if cfg.get("pool") is not None else ("res" if res is not None else ("up" if cfg.get("up") is not None else None))
+        tail = "pool" if spec.pool is not None else ("res" if res is not None else ("up" if spec.up is not None else None))
         if tail is not None and (not has_bn or fused1):
             raise RuntimeError("conv_bn_act: residual / pool / upsample need a BatchNorm layer on the MFMA path")
-        za = None
         if fused1:
             # Cin = 1 conv + BatchNorm(train) + activation: the pre-BatchNorm tensor is never stored (recomputed from x where needed)
             coef = torch.empty((4, Cout), device=dev, dtype=torch.float32)
@@ -809,13 +850,13 @@ class _ConvBnAct(torch.autograd.Function):
             stat = _scratch("stat", 2 * Cout * d["nblk"], dev)
             _lib.check(lib.viai_conv2d_cin1_bn_fwd(d["ref"], x.data_ptr(), _ptr(xmask), wp.data_ptr(), 0, stat.data_ptr(), 0, 0, 0, act, 0, st),
                        "viai_conv2d_cin1_bn_fwd")
-            _bn_finalize(lib, d, stat, M, Cout, gamma, beta, rmean, rvar, nbt, cfg, coef, st)
+            _bn_finalize(lib, d, stat, M, Cout, gamma, beta, rmean, rvar, nbt, {"momentum": spec.momentum, "eps": spec.eps}, coef, st)
             z = torch.empty((N, OH, OW, Cout), device=dev, dtype=torch.float32)
-            za = _amax_slot(dev)
-            if cfg.get("p16_out") and P16 and act in (ACT_NONE, ACT_RELU, ACT_LRELU):
+            za = out.za = _amax_slot(dev)
+            if spec.p16_out and P16 and act in (ACT_NONE, ACT_RELU, ACT_LRELU):
                 _lib.check(lib.viai_conv2d_cin1_bn_fwd_p16(d["ref"], x.data_ptr(), _ptr(xmask), wp.data_ptr(), 0, sc, sh, gamma.data_ptr(), beta.data_ptr(), M,
                                                            z.data_ptr(), act, za.data_ptr(), st), "viai_conv2d_cin1_bn_fwd_p16")
-                cfg["z_p16"] = True
+                out.z_p16 = True
             else:
                 _lib.check(lib.viai_conv2d_cin1_bn_fwd(d["ref"], x.data_ptr(), _ptr(xmask), wp.data_ptr(), 0, 0, sc, sh, z.data_ptr(), act, za.data_ptr(), st),
                            "viai_conv2d_cin1_bn_fwd")
@@ -823,19 +864,18 @@ class _ConvBnAct(torch.autograd.Function):
         elif has_bn:
             y = torch.empty((N, OH, OW, Cout), device=dev, dtype=torch.float32)
             coef = torch.empty((4, Cout), device=dev, dtype=torch.float32)   # mean, invstd, scale, shift
-            _conv_bn_coef(lib, d, caps, x, x2, xp, xa, wp, bias, (gamma, beta, rmean, rvar, nbt), cfg, y, coef, st)
-            za = _amax_slot(dev)
-            p16_out = bool(cfg.get("p16_out") and P16 and training and Cout % 32 == 0)
-            z, extra = _TAILS[tail](lib, cfg, y, coef, gamma, beta, res, (N, OH, OW, Cout), act, p16_out, za, st)
+            _conv_bn_coef(lib, d, caps, x, x2, xp, xa, wp, bias, (gamma, beta, rmean, rvar, nbt), spec, y, coef, st)
+            out.za = _amax_slot(dev)
+            p16_out = bool(spec.p16_out and P16 and training and Cout % 32 == 0)
+            z, extra, out.z_p16, out.z_twin = _TAILS[tail](lib, spec, y, coef, gamma, beta, res, (N, OH, OW, Cout), act, p16_out, out.za, st)
             ctx.save_for_backward(x, x2, weight, y, coef, *extra)
         else:
             z = torch.empty((N, OH, OW, Cout), device=dev, dtype=torch.float32)
             _conv_fwd(lib, d, x, x2, xp, xa, wp, bias, z, 0, act, st)
             if act == ACT_SIGMOID:
-                za = _const_amax(dev, 1.0)
+                out.za = _const_amax(dev, 1.0)
             ctx.save_for_backward(x, x2, weight, z, None)
-        cfg["za"] = za                       # conv_bn_act attaches it to the returned tensor
-        ctx.state = _LayerState(d, cfg, has_bn, bias is not None, (N, IH, IW, C1, C2, Cout, OH, OW), xa, fused1, tail, xp, x_twin_w, xmask)
+        ctx.state = _LayerState(d, spec, has_bn, bias is not None, (N, IH, IW, C1, C2, Cout, OH, OW), xa, fused1, tail, xp, x_twin_w)
         return z
 
     @staticmethod
@@ -844,11 +884,11 @@ class _ConvBnAct(torch.autograd.Function):
         s = ctx.state
         saved = ctx.saved_tensors
         x, x2, weight, y_or_z, coef = saved[:5]
-        cfg, tail = s.cfg, s.tail
+        spec, tail = s.spec, s.tail
         st = _stream()
         addend = _take_addend(ctx)
         dz = _c(dz)
-        act = cfg["act"]
+        act = spec.act
         # (the pool tail takes two addends as well -- viai_bn_act_pool_bwd_amax2.  With the per-pixel apply pass, which gathered up to four windows per pixel,
         # two tensors to gather cost more than the add they save (103.5 against 102.2 ms on the vision-infused step); with the 2 x 2-block pass it is a
         # small gain: 102.17 -> 101.99, two same-box pairs)
@@ -861,7 +901,7 @@ class _ConvBnAct(torch.autograd.Function):
         need_x, need_x2, need_w, need_b = needs[:4]
         want_amax, form = False, DY_PLAIN
         if s.has_bn:
-            want_amax, form = _dy_form(_caps(s.d), need_x, need_w, need_b, act, tail, s.has_bias, cfg["training"], s.dims[5], P16, F16_BACKWARD, JOIN_FUSED)
+            want_amax, form = _dy_form(_caps(s.d), need_x, need_w, need_b, act, tail, s.has_bias, spec.training, s.dims[5], P16, F16_BACKWARD, JOIN_FUSED)
         # 1. the gradient through the tail, down to the BatchNorm's output
         dz, dres, act = _tail_bwd(lib, s, form, act, dz, addend, saved, st)
         # 2. through BatchNorm + activation (or the activation alone): dy, the gradient of the conv's output, in the chosen form
@@ -877,9 +917,9 @@ class _ConvBnAct(torch.autograd.Function):
         xw, xwa, xwp = x, s.xa, s.x_p16
         if s.x_twin_w is not None and need_w:
             xw, xwa, xwp = s.x_twin_w, amax_of(s.x_twin_w), True          # planes for the weight gradient (the forward read the fp32 tensor)
-        dx, dx2, dw, db = _conv_grads(lib, s.d, cfg, s.dims, s.has_bn, s.has_bias, (need_x, need_x2, need_w, need_b), xwa,
+        dx, dx2, dw, db = _conv_grads(lib, s.d, spec, s.dims, s.has_bn, s.has_bias, (need_x, need_x2, need_w, need_b), xwa,
                                       xw, x2, weight, dy, amax, st, dy_p16=form in (DY_PLANES, DY_JOIN), x_p16=xwp, dy_w=dy_w)
-        return dx, dx2, dw, db, dgamma, dbeta, None, None, None, dres, None
+        return dx, dx2, dw, db, dgamma, dbeta, None, None, None, dres, None, None, None
 
 
 def _tail_bwd(lib, s, form, act, dz, addend, saved, st):
@@ -888,7 +928,7 @@ def _tail_bwd(lib, s, form, act, dz, addend, saved, st):
     backward: nothing to launch here (the join only gets its dres tensor)."""
     if s.tail == "up":
         N, _, _, _, _, Cout, OH, OW = s.dims
-        UH, UW = s.cfg["up"]
+        UH, UW = s.spec.up
         dlo = torch.empty((N, OH, OW, Cout), device=dz.device, dtype=torch.float32)
         _lib.check(lib.viai_bilinear_ac_bwd(dz.data_ptr(), dlo.data_ptr(), N, OH, OW, UH, UW, Cout, st), "viai_bilinear_ac_bwd")
         return dlo, None, act
@@ -918,7 +958,7 @@ def _bn_bwd(lib, s, form, want_amax, act, dz, addend, saved, dres, needs, st):
     rows = 2 if form in (DY_PLAIN, DY_POOL) else 3       # (the passes that write planes reduce max |dy| per channel as well)
     part = _scratch("bnpart", rows * Cout * nblk, dev)
     sums = _scratch("bnsums", rows * Cout, dev)
-    pg, pb, dgamma, dbeta, flags = _bn_targets(s.cfg.get("gt") or (None, None, None, None), needs[4], needs[5], s.cfg["training"], Cout, dev)
+    pg, pb, dgamma, dbeta, flags = _bn_targets(s.spec.gt, needs[4], needs[5], s.spec.training, Cout, dev)
     dy = torch.empty_like(y if form == DY_POOL else dz)
     amax = _amax_slot(dev) if want_amax else None
     dy_w = None
@@ -933,7 +973,7 @@ def _bn_bwd(lib, s, form, want_amax, act, dz, addend, saved, dres, needs, st):
     elif form == DY_PLANES:
         _lib.check(lib.viai_bn_act_bwd_p16(dz.data_ptr(), y.data_ptr(), *mid, dy.data_ptr(), M, Cout, act, 0.2, flags, amax.data_ptr(), st), "viai_bn_act_bwd_p16")
     elif form == DY_POOL:
-        k_, s_, p_ = s.cfg["pool"]
+        k_, s_, p_ = s.spec.pool
         # (the pooled gradient may have arrived as two addends -- ops.fork2: the stem's output feeds layer1's conv1 and its first join -- summed on load)
         _lib.check(lib.viai_bn_act_pool_bwd_amax2(dz.data_ptr(), _ptr(addend), saved[5].data_ptr(), N, OH, OW, k_, s_, p_, y.data_ptr(), *mid, dy.data_ptr(),
                                                   Cout, act, 0.2, flags, _ptr(amax), st), "viai_bn_act_pool_bwd")
@@ -951,22 +991,21 @@ CIN1_WGRAD_MAIN = True
 def _backward_cin1(s, needs, lib, dz, x, weight, coef, st):
     """backward of the fused Cin = 1 conv + BatchNorm(train) + activation layer: y is recomputed from x; dy is written to memory only
     when a data gradient needs it (the frozen-D pass of the G step), the weight gradient forms it on the fly."""
-    d, cfg, xmask = s.d, s.cfg, s.xmask
+    d, spec = s.d, s.spec
     N, IH, IW, C1, C2, Cout, OH, OW = s.dims
     dev = dz.device
-    act = cfg["act"]
+    act, xmask, gt = spec.act, spec.xmask, spec.gt
     need_x, _, need_w, _, need_g, need_be = needs
-    gt = cfg.get("gt") or (None, None, None, None)
     wp = _packed(weight, d, 0, st)
     mean, invstd, sc, sh = _rows(coef)
     part = _scratch("bnpart1", 2 * Cout * d["nblk"], dev)
     sums = torch.empty(2 * Cout, device=dev, dtype=torch.float32)     # private: the trailing weight gradient reads it
-    pg, pb, dgamma, dbeta, flags = _bn_targets(gt, need_g, need_be, cfg["training"], Cout, dev)
+    pg, pb, dgamma, dbeta, flags = _bn_targets(gt, need_g, need_be, spec.training, Cout, dev)
     # the data gradient straight from dz (viai_conv2d_cin1_bn_dgrad).  Windows of one row (D.conv1: 1 x 4, the frozen-D pass of the G step)
     # take the single-pass kernel -- thread = output pixel, dz read once, no dy tensor: 55 + 80 us -> one pass over dz.  Other windows map
     # threads to INPUT pixels and recompute y per contributing output pixel: measured SLOWER than writing dy once with the recomputing
     # apply pass (7.48 - 7.50 vs 7.38 - 7.40 ms per step), so there it stays opt-in (VIAI_CIN1_BN_DGRAD=1; =0 switches both off)
-    one_row = (cfg["k"][0] == 1 and cfg["s"][0] == 1 and cfg["p"][0] == 0 and not cfg["transposed"])
+    one_row = (spec.k[0] == 1 and spec.s[0] == 1 and spec.p[0] == 0 and not spec.transposed)
     fused_dx = need_x and os.environ.get("VIAI_CIN1_BN_DGRAD", "1" if one_row else "0") != "0"
     dy = torch.empty_like(dz) if (need_x and not fused_dx) else None
     _lib.check(lib.viai_conv2d_cin1_bn_bwd(d["ref"], x.data_ptr(), _ptr(xmask), wp.data_ptr(), 0, dz.data_ptr(), mean, invstd, sc, sh, part.data_ptr(),
@@ -995,16 +1034,14 @@ def _backward_cin1(s, needs, lib, dz, x, weight, coef, st):
         if xmask is not None:                                   # d/ds of conv(s * mask)
             N_, T_ = xmask.shape[0], xmask.shape[-1]
             _lib.check(lib.viai_mask_mul(dx.data_ptr(), xmask.data_ptr(), dx.data_ptr(), N_, dx.numel() // (N_ * T_), T_, st), "viai_mask_mul")
-    return dx, None, dw, None, dgamma, dbeta, None, None, None, None, None
+    return dx, None, dw, None, dgamma, dbeta, None, None, None, None, None, None, None
 
 
-def _cin1_fused_applies(x, weight, bias, bn, kernel, stride, padding, transposed, training):
+def _cin1_fused_applies(x, weight, bias, bn, spec):
     """will this call take the fused Cin = 1 conv + BatchNorm(train) layer?  (the predicate of _ConvBnAct.forward)"""
-    if bn is None or not training or bias is not None or x.shape[3] != 1 or not isinstance(bn, torch.nn.modules.batchnorm._BatchNorm):
+    if bn is None or not spec.training or bias is not None or x.shape[3] != 1 or not isinstance(bn, torch.nn.modules.batchnorm._BatchNorm):
         return False
-    Cout = weight.shape[1] if transposed else weight.shape[0]
-    d = conv_desc(x.shape[0], x.shape[1], x.shape[2], 1, 0, Cout, kernel[0], kernel[1], stride[0], stride[1], padding[0], padding[1], 1 if transposed else 0)
-    return _caps(d).cin1_bn
+    return _caps(_layer_desc(x.shape, 0, weight, spec.k, spec.s, spec.p, spec.transposed)).cin1_bn
 
 
 def conv_bn_act(x, weight, bias=None, bn=None, *, kernel, stride=(1, 1), padding=(0, 0), transposed=False,
@@ -1025,36 +1062,16 @@ def conv_bn_act(x, weight, bias=None, bn=None, *, kernel, stride=(1, 1), padding
         raise ValueError("conv_bn_act: upsample takes a BatchNorm layer on the MFMA path (see upsample_fusable) and excludes residual / pool")
     if xmask is not None:
         xmask = _c(xmask.reshape(xmask.shape[0], xmask.shape[-1]))
-        trainmode = training if (bn is None or (bn.track_running_stats and bn.running_mean is not None)) else True
-        if not (x2 is None and tuple(dilation) == (1, 1) and tuple(padding2) == (-1, -1)
-                and _cin1_fused_applies(x, weight, bias, bn, tuple(kernel), tuple(stride), tuple(padding), transposed, trainmode)):
-            x = mask_mul(x, xmask)
-            xmask = None
-    cfg = {"k": tuple(kernel), "s": tuple(stride), "p": tuple(padding), "transposed": bool(transposed),
-           "act": int(act), "training": bool(training), "momentum": 0.1, "eps": BN_EPS,
-           "d": tuple(dilation), "p2": tuple(padding2), "xa_in": (amax_of(x), amax_of(x2)), "xmask": xmask,
-           "pool": tuple(int(v) for v in pool) if pool is not None else None,
-           "up": (int(upsample[0]), int(upsample[1])) if upsample is not None else None,
-           "p16_out": bool(out_p16) and bn is not None and isinstance(bn, torch.nn.modules.batchnorm._BatchNorm) and bn.weight is not None,
-           "x_twin": getattr(x, "_viai_twin", None) if x2 is None else None}
+    spec, bn_args = _layer_spec((weight, bias), bn, kernel=kernel, stride=stride, padding=padding, transposed=transposed, act=act, training=training,
+                              dilation=dilation, padding2=padding2, xmask=xmask, pool=pool, upsample=upsample, out_p16=out_p16, xa_in=(amax_of(x), amax_of(x2)))
+    if xmask is not None and not (x2 is None and spec.d == (1, 1) and spec.p2 == (-1, -1) and _cin1_fused_applies(x, weight, bias, bn, spec)):
+        x = mask_mul(x, xmask)                            # (the magnitude carries over: spec.xa_in stands)
+        spec = spec._replace(xmask=None)
+    out = _LayerOut()
+    z = _tag_amax(_ConvBnAct.apply(x, x2, weight, bias, *bn_args, residual, spec, getattr(x, "_viai_twin", None) if x2 is None else None, out), out)
     if bn is not None:
-        cfg["momentum"] = 0.1 if bn.momentum is None else float(bn.momentum)
-        cfg["eps"] = float(bn.eps)
-        track = bn.track_running_stats and bn.running_mean is not None
-        if not training and not track:
-            cfg["training"] = True
-        if DIRECT_GRAD:
-            cfg["gt"] = tuple(p.grad if (p is not None and p.is_leaf and p.requires_grad and p.grad is not None) else None
-                              for p in (weight, bias, bn.weight, bn.bias))
-        z = _tag_amax(_ConvBnAct.apply(x, x2, weight, bias, bn.weight, bn.bias,
-                                       bn.running_mean if track else None, bn.running_var if track else None,
-                                       bn.num_batches_tracked if (track and cfg["training"]) else None, residual, cfg), cfg)
         z._viai_lazy_sum_ok = True                        # its backward takes a gradient with an addend attached (fork2)
-        return z
-    if DIRECT_GRAD:
-        cfg["gt"] = tuple(p.grad if (p is not None and p.is_leaf and p.requires_grad and p.grad is not None) else None
-                          for p in (weight, bias, None, None))
-    return _tag_amax(_ConvBnAct.apply(x, x2, weight, bias, None, None, None, None, None, None, cfg), cfg)
+    return z
 
 
 FUSE_BN_UP = True      # BatchNorm apply + the resize behind a decoder block in one pass (module switch: tests/test_kernels_gpu.py flips it)
@@ -1075,15 +1092,11 @@ def upsample_fusable(x, weight, bias, bn, transposed, act, size=None):
     return cout % 4 == 0 and 1 <= c4 <= 256 and (c4 & (c4 - 1)) == 0
 
 
-def _tag_amax(z, cfg):
-    za = cfg.pop("za", None)
-    if za is not None:
-        z._viai_amax = za
-    if cfg.pop("z_p16", False):
-        z._viai_p16 = True
-    zt = cfg.pop("z_twin", None)
-    if zt is not None:
-        z._viai_twin = zt
+def _tag_amax(z, out):
+    """the one place that turns what a forward handed back (_LayerOut) into the tags of its output tensor"""
+    for tag, v in zip(_Z_TAGS, (out.za, out.z_p16, out.z_twin)):
+        if v is not None:
+            setattr(z, tag, v)
     return z
 
 
@@ -1100,7 +1113,7 @@ class _ConvBnActCout1(torch.autograd.Function):
     (the BatchNorm backward forms it from du in registers) -- csrc/conv_direct.hip `viai_pair_cout1_*`."""
 
     @staticmethod
-    def forward(ctx, x, x2, w1, b1, gamma, beta, rmean, rvar, nbt, w2, b2, cfg):
+    def forward(ctx, x, x2, w1, b1, gamma, beta, rmean, rvar, nbt, w2, b2, spec):
         lib = _lib.load()
         xp = is_p16(x)
         _require(None if xp else x, x2, w1, b1, gamma, beta, w2, b2)
@@ -1108,12 +1121,9 @@ class _ConvBnActCout1(torch.autograd.Function):
         x2 = _c(x2) if x2 is not None else None
         N, IH, IW, C1 = x.shape
         C2 = x2.shape[3] if x2 is not None else 0
-        kh, kw = cfg["k"]
-        tr1 = cfg["transposed"]
-        Cmid = w1.shape[1] if tr1 else w1.shape[0]
-        d = conv_desc(N, IH, IW, C1, C2, Cmid, kh, kw, cfg["s"][0], cfg["s"][1], cfg["p"][0], cfg["p"][1], 1 if tr1 else 0)
-        OH, OW = d["OH"], d["OW"]
-        d2 = conv_desc(N, OH, OW, Cmid, 0, 1, 3, 3, 1, 1, 1, 1, 1 if cfg["transposed2"] else 0)
+        d = _layer_desc(x.shape, C2, w1, spec.k, spec.s, spec.p, spec.transposed)
+        C1, Cmid, OH, OW = d["desc"].C1, d["desc"].Cout, d["OH"], d["OW"]
+        d2 = conv_desc(N, OH, OW, Cmid, 0, 1, 3, 3, 1, 1, 1, 1, 1 if spec.transposed2 else 0)
         st = _stream()
         dev = x.device
         M = N * OH * OW
@@ -1122,10 +1132,10 @@ class _ConvBnActCout1(torch.autograd.Function):
         wp1 = _packed(w1, d, 0, st)
         wp2 = _packed(w2, d2, 0, st)
         caps = _caps(d)
-        x, xp, xa = _stage_input(d, caps, x, x2, xp, cfg, st)
+        x, xp, xa = _stage_input(d, caps, x, x2, xp, spec.xa_in, st)
         y = torch.empty((N, OH, OW, Cmid), device=dev, dtype=torch.float32)
         coef = torch.empty((4, Cmid), device=dev, dtype=torch.float32)       # mean, invstd, scale, shift
-        _conv_bn_coef(lib, d, caps, x, x2, xp, xa, wp1, b1, (gamma, beta, rmean, rvar, nbt), cfg, y, coef, st)
+        _conv_bn_coef(lib, d, caps, x, x2, xp, xa, wp1, b1, (gamma, beta, rmean, rvar, nbt), spec, y, coef, st)
         sc, sh = _rows(coef)[2:]
         p = torch.empty((N, OH, OW, 1), device=dev, dtype=torch.float32)
         if PAIR_FWD_FUSED and Cmid <= 64:
@@ -1135,64 +1145,61 @@ class _ConvBnActCout1(torch.autograd.Function):
             # Standalone (tools/profile_pair.py): G.conv6_1 -> conv6_2 (32 channels, 256 x 256) 62 us against 46 + 57 for the two
             # launches; D.conv3 -> conv4 (512 channels on 64 x 32 maps) 67 us against 24 + 38 -- a whole wave per pixel leaves four
             # lane groups per block and 12 dependent load rounds each, so wide layers keep the two launches
-            _lib.check(lib.viai_pair_cout1_fwd(d2["ref"], y.data_ptr(), sc, sh, cfg["act"], wp2.data_ptr(),
-                                               _ptr(b2), p.data_ptr(), cfg["act2"], st), "viai_pair_cout1_fwd")
+            _lib.check(lib.viai_pair_cout1_fwd(d2["ref"], y.data_ptr(), sc, sh, spec.act, wp2.data_ptr(),
+                                               _ptr(b2), p.data_ptr(), spec.act2, st), "viai_pair_cout1_fwd")
         elif PAIR_FWD_DOTS:
             # wide front layers (D.conv3 -> conv4): one grid-stride pass over y leaves the nine tap products of every pixel, a gather sums
             # them: no z, y read once (was: bn_act_fwd 22 us + the row-run forward 36 us on the 67 MB tensor)
             ws = _scratch("pairdots", 9 * M, dev)
-            _lib.check(lib.viai_pair_cout1_fwd_dots(d2["ref"], y.data_ptr(), sc, sh, cfg["act"], wp2.data_ptr(),
-                                                    _ptr(b2), ws.data_ptr(), p.data_ptr(), cfg["act2"], st), "viai_pair_cout1_fwd_dots")
+            _lib.check(lib.viai_pair_cout1_fwd_dots(d2["ref"], y.data_ptr(), sc, sh, spec.act, wp2.data_ptr(),
+                                                    _ptr(b2), ws.data_ptr(), p.data_ptr(), spec.act2, st), "viai_pair_cout1_fwd_dots")
         else:
             # z exists only between these two launches: the backward works from y
             z = torch.empty_like(y)
-            _lib.check(lib.viai_bn_act_fwd(y.data_ptr(), sc, sh, z.data_ptr(), M, Cmid, cfg["act"], 0.2, st),
+            _lib.check(lib.viai_bn_act_fwd(y.data_ptr(), sc, sh, z.data_ptr(), M, Cmid, spec.act, 0.2, st),
                        "viai_bn_act_fwd")
-            _lib.check(lib.viai_conv2d_fwd(d2["ref"], z.data_ptr(), 0, wp2.data_ptr(), _ptr(b2), p.data_ptr(), 0, cfg["act2"], st),
+            _lib.check(lib.viai_conv2d_fwd(d2["ref"], z.data_ptr(), 0, wp2.data_ptr(), _ptr(b2), p.data_ptr(), 0, spec.act2, st),
                        "viai_conv2d_fwd")
             del z
         ctx.save_for_backward(x, x2, w1, y, coef, w2, p)
-        ctx.d, ctx.d2, ctx.cfg, ctx.xa = d, d2, cfg, xa
-        ctx.x_p16 = xp
-        ctx.has_bias, ctx.has_bias2 = b1 is not None, b2 is not None
-        ctx.dims = (N, IH, IW, C1, C2, Cmid, OH, OW)
+        ctx.state = _LayerState(d, spec, True, b1 is not None, (N, IH, IW, C1, C2, Cmid, OH, OW), xa, x_p16=xp, d2=d2, has_bias2=b2 is not None)
         return p
 
     @staticmethod
     def backward(ctx, dp):
         lib = _lib.load()
         x, x2, w1, y, coef, w2, p = ctx.saved_tensors
-        d, d2, cfg = ctx.d, ctx.d2, ctx.cfg
-        N, IH, IW, C1, C2, Cmid, OH, OW = ctx.dims
+        s = ctx.state
+        d, d2, spec = s.d, s.d2, s.spec
+        N, IH, IW, C1, C2, Cmid, OH, OW = s.dims
         M = N * OH * OW
         st = _stream()
         dev = dp.device
         dp = _c(dp)
         need_x, need_x2, need_w1, need_b1, need_g, need_be = ctx.needs_input_grad[:6]
         need_w2, need_b2 = ctx.needs_input_grad[9], ctx.needs_input_grad[10]
-        gt = cfg.get("gt") or (None, None, None, None)
-        gt2 = cfg.get("gt2") or (None, None)
+        gt, gt2 = spec.gt, spec.gt2
         # du = gradient of the Cout = 1 layer's pre-activation output (N, OH, OW, 1): 4 bytes per pixel
-        if cfg["act2"] == ACT_NONE:
+        if spec.act2 == ACT_NONE:
             du = dp
         else:
             du = torch.empty_like(dp)
-            _lib.check(lib.viai_act_bwd_from_output(dp.data_ptr(), p.data_ptr(), du.data_ptr(), dp.numel(), cfg["act2"], 0.2, st),
+            _lib.check(lib.viai_act_bwd_from_output(dp.data_ptr(), p.data_ptr(), du.data_ptr(), dp.numel(), spec.act2, 0.2, st),
                        "viai_act_bwd_from_output")
         wp2 = _packed(w2, d2, 0, st)
         # ---- the Cout = 1 layer's own parameter gradients
         dw2 = db2 = None
-        if need_w2 or (need_b2 and ctx.has_bias2):
+        if need_w2 or (need_b2 and s.has_bias2):
             acc_w2 = gt2[0] is not None and need_w2
             dw2 = gt2[0] if acc_w2 else torch.empty_like(w2)
             acc_b2 = False
-            if ctx.has_bias2 and need_b2:
+            if s.has_bias2 and need_b2:
                 acc_b2 = gt2[1] is not None
                 db2 = gt2[1] if acc_b2 else torch.empty(1, device=dev, dtype=torch.float32)
             side, handle = _wgrad_side(acc_w2 and (acc_b2 or db2 is None), st)
             ws = _scratch("wgrad", d2["ws_floats"] + lib.viai_colsum_blocks(M, 1) + 8, dev, side)
             if need_w2:
-                _lib.check(lib.viai_pair_cout1_wgrad(d2["ref"], y.data_ptr(), *_rows(coef)[2:], cfg["act"], du.data_ptr(),
+                _lib.check(lib.viai_pair_cout1_wgrad(d2["ref"], y.data_ptr(), *_rows(coef)[2:], spec.act, du.data_ptr(),
                                                      ws.data_ptr(), dw2.data_ptr(), 1 if acc_w2 else 0, handle), "viai_pair_cout1_wgrad")
             if db2 is not None:
                 _lib.check(lib.viai_colsum(du.data_ptr(), M, 1, ws[d2["ws_floats"]:].data_ptr(), db2.data_ptr(), 1 if acc_b2 else 0, handle),
@@ -1208,22 +1215,22 @@ class _ConvBnActCout1(torch.autograd.Function):
         if nblk is None:
             nblk = d2["pair_blk"] = int(lib.viai_pair_cout1_bn_bwd_blocks(d2["ref"]))
         # (this op counts either source's gradient as the data gradient; it has no pass that writes both forms: planes or fp32)
-        want_amax, form = _dy_form(_caps(d), need_x or need_x2, need_w1, need_b1, cfg["act"], None, ctx.has_bias, cfg["training"], Cmid, P16, F16_BACKWARD, JOIN_FUSED)
+        want_amax, form = _dy_form(_caps(d), need_x or need_x2, need_w1, need_b1, spec.act, None, s.has_bias, spec.training, Cmid, P16, F16_BACKWARD, JOIN_FUSED)
         dy_p16 = form == DY_PLANES
         rows = 3 if dy_p16 else 2
         part = _scratch("bnpart", rows * Cmid * nblk, dev)
         sums = _scratch("bnsums", rows * Cmid, dev)
-        pg, pb, dgamma, dbeta, flags = _bn_targets(gt, need_g, need_be, cfg["training"], Cmid, dev)
+        pg, pb, dgamma, dbeta, flags = _bn_targets(gt, need_g, need_be, spec.training, Cmid, dev)
         amax = _amax_slot(dev) if want_amax else None
-        want_dy = need_x or need_x2 or need_w1 or (need_b1 and ctx.has_bias)
+        want_dy = need_x or need_x2 or need_w1 or (need_b1 and s.has_bias)
         dy = torch.empty_like(y) if want_dy else None
         fn = lib.viai_pair_cout1_bn_bwd_p16 if dy_p16 else lib.viai_pair_cout1_bn_bwd
-        _lib.check(fn(d2["ref"], du.data_ptr(), wp2.data_ptr(), y.data_ptr(), *_rows(coef), cfg["act"], part.data_ptr(), sums.data_ptr(), _ptr(pg), _ptr(pb),
+        _lib.check(fn(d2["ref"], du.data_ptr(), wp2.data_ptr(), y.data_ptr(), *_rows(coef), spec.act, part.data_ptr(), sums.data_ptr(), _ptr(pg), _ptr(pb),
                       _ptr(dy), flags, _ptr(amax), st), "viai_pair_cout1_bn_bwd")
         dx = dx2 = dw1 = db1 = None
         if want_dy:
-            dx, dx2, dw1, db1 = _conv_grads(lib, d, cfg, ctx.dims, True, ctx.has_bias, (need_x, need_x2, need_w1, need_b1), ctx.xa,
-                                            x, x2, w1, dy, amax, st, dy_p16=dy_p16, x_p16=ctx.x_p16)
+            dx, dx2, dw1, db1 = _conv_grads(lib, d, spec, s.dims, True, s.has_bias, (need_x, need_x2, need_w1, need_b1), s.xa,
+                                            x, x2, w1, dy, amax, st, dy_p16=dy_p16, x_p16=s.x_p16)
         return dx, dx2, dw1, db1, dgamma, dbeta, None, None, None, dw2, db2, None
 
 
@@ -1233,11 +1240,8 @@ def conv_bn_act_cout1_ok(x, weight, bn, conv2_weight, *, kernel, stride, padding
         return False
     if tuple(kernel2) != (3, 3) or tuple(stride2) != (1, 1) or tuple(padding2) != (1, 1):
         return False
-    N, IH, IW, C1 = x.shape
-    C2 = x2.shape[3] if x2 is not None else 0
-    Cmid = weight.shape[1] if transposed else weight.shape[0]
-    d = conv_desc(N, IH, IW, C1, C2, Cmid, kernel[0], kernel[1], stride[0], stride[1], padding[0], padding[1], 1 if transposed else 0)
-    d2 = conv_desc(N, d["OH"], d["OW"], Cmid, 0, 1, 3, 3, 1, 1, 1, 1, 0)
+    d = _layer_desc(x.shape, x2.shape[3] if x2 is not None else 0, weight, kernel, stride, padding, transposed)
+    d2 = conv_desc(x.shape[0], d["OH"], d["OW"], d["desc"].Cout, 0, 1, 3, 3, 1, 1, 1, 1, 0)
     ok = d2.get("pair_ok")
     if ok is None:
         ok = d2["pair_ok"] = bool(_lib.load().viai_pair_cout1_ok(d2["ref"]))
@@ -1247,19 +1251,9 @@ def conv_bn_act_cout1_ok(x, weight, bn, conv2_weight, *, kernel, stride, padding
 def conv_bn_act_cout1(x, weight, bias, bn, weight2, bias2, *, kernel, stride=(1, 1), padding=(0, 0), transposed=False, act=ACT_NONE,
                       transposed2=False, act2=ACT_NONE, x2=None, training=True):
     """the fused pair on NHWC tensors (check conv_bn_act_cout1_ok first)"""
-    cfg = {"k": tuple(kernel), "s": tuple(stride), "p": tuple(padding), "transposed": bool(transposed), "act": int(act), "training": bool(training),
-           "momentum": 0.1 if bn.momentum is None else float(bn.momentum), "eps": float(bn.eps), "transposed2": bool(transposed2),
-           "act2": int(act2), "xa_in": (amax_of(x), amax_of(x2))}
-    track = bn.track_running_stats and bn.running_mean is not None
-    if not training and not track:
-        cfg["training"] = True
-    if DIRECT_GRAD:
-        def tgt(p):
-            return p.grad if (p is not None and p.is_leaf and p.requires_grad and p.grad is not None) else None
-        cfg["gt"] = tuple(tgt(p) for p in (weight, bias, bn.weight, bn.bias))
-        cfg["gt2"] = (tgt(weight2), tgt(bias2))
-    out = _ConvBnActCout1.apply(x, x2, weight, bias, bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None,
-                                bn.num_batches_tracked if (track and cfg["training"]) else None, weight2, bias2, cfg)
+    spec, bn_args = _layer_spec((weight, bias), bn, kernel=kernel, stride=stride, padding=padding, transposed=transposed, act=act, training=training,
+                                  xa_in=(amax_of(x), amax_of(x2)), params2=(weight2, bias2), transposed2=transposed2, act2=act2)
+    out = _ConvBnActCout1.apply(x, x2, weight, bias, *bn_args, weight2, bias2, spec)
     if act2 == ACT_SIGMOID:
         out._viai_amax = _const_amax(x.device, 1.0)
     return out
@@ -1518,7 +1512,7 @@ def fork2(x):
     node._viai_addend_slot = slot
     a, b = _Fork2.apply(x, slot)
     for t in (a, b):                                      # the tags conv_bn_act left for the next layer
-        for k in ("_viai_amax", "_viai_twin", "_viai_p16"):
+        for k in _Z_TAGS:
             v = getattr(x, k, None)
             if v is not None:
                 setattr(t, k, v)

@@ -20,6 +20,7 @@ The registered backward is an op of its own, `torch.ops.viai.conv_bn_act_backwar
 a CPU tensor raises.  `ops.begin_step(device)` must have been called once per step (it re-arms the magnitude slots), as the networks do."""
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import List, Optional, Tuple
 
 import torch
@@ -41,12 +42,6 @@ class _Ctx:
         self.saved_tensors = tensors
 
 
-def _cfg(kernel, stride, padding, transposed, act, training, momentum, eps):
-    return {"k": tuple(kernel), "s": tuple(stride), "p": tuple(padding), "transposed": bool(transposed), "act": int(act), "training": bool(training),
-            "momentum": float(momentum), "eps": float(eps), "d": (1, 1), "p2": (-1, -1), "xa_in": (None, None), "xmask": None, "pool": None, "up": None,
-            "p16_out": False, "x_twin": None}
-
-
 def _empty(dev):
     return torch.empty(0, device=dev, dtype=torch.float32)
 
@@ -58,15 +53,16 @@ def _conv_bn_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
                  eps: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     if ops.is_p16(x):
         raise ValueError("torch.ops.viai.conv_bn_act takes fp32 tensors (pre-split P16 tensors stay inside viai_amd.ops.conv_bn_act)")
-    ctx = _Ctx((True, False, True, bias is not None, gamma is not None, beta is not None, False, False, False, False, False))
-    cfg = _cfg(kernel, stride, padding, transposed, act, training, momentum, eps)
+    ctx = _Ctx((True, False, True, bias is not None, gamma is not None, beta is not None) + (False,) * 7)
     track = running_mean is not None and running_var is not None
-    if gamma is not None and not training and not track:
-        cfg["training"] = True                                                   # nn.BatchNorm2d without running statistics normalises with batch statistics
-    # a FUNCTIONAL op (torch.library registers autograd formulas for those only): the kernels update copies of the running statistics, which are returned
+    # a FUNCTIONAL op (torch.library registers autograd formulas for those only): the kernels update copies of the running statistics, which are returned,
+    # and no gradient is written in place (direct=False)
     rm = running_mean.clone() if track else None
     rv = running_var.clone() if track else None
-    z = ops._ConvBnAct.forward(ctx, x, None, weight, bias, gamma, beta, rm, rv, None, None, cfg)
+    bn = None if gamma is None else SimpleNamespace(weight=gamma, bias=beta, running_mean=rm, running_var=rv, num_batches_tracked=None,
+                                                    track_running_stats=track, momentum=momentum, eps=eps)
+    spec, bn_args = ops._layer_spec((weight, bias), bn, kernel=kernel, stride=stride, padding=padding, transposed=transposed, act=act, training=training, direct=False)
+    z = ops._ConvBnAct.forward(ctx, x, None, weight, bias, *bn_args, None, spec, None, ops._LayerOut())
     y, coef, xa = ctx.saved_tensors[3], ctx.saved_tensors[4], ctx.state.xa
     dev = x.device
     # outputs must not alias each other: without BatchNorm the saved map IS z (the backward op takes z for it)
@@ -97,17 +93,13 @@ def _conv_bn_act_backward(dz: torch.Tensor, x: torch.Tensor, weight: torch.Tenso
                           has_bias: bool, kernel: List[int], stride: List[int], padding: List[int], transposed: bool, act: int, training: bool,
                           momentum: float, eps: float, needs: List[bool]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     has_bn = coef.numel() > 0
-    cfg = _cfg(kernel, stride, padding, transposed, act, training, momentum, eps)
-    N, IH, IW, C1 = x.shape
-    cout = weight.shape[1] if transposed else weight.shape[0]
-    cin_w = weight.shape[0] if transposed else weight.shape[1]
-    if C1 == 4 and 1 < cin_w < 4:
-        C1 = cin_w
-    d = ops.conv_desc(N, IH, IW, C1, 0, cout, kernel[0], kernel[1], stride[0], stride[1], padding[0], padding[1], 1 if transposed else 0)
+    spec, _ = ops._layer_spec((weight, None), None, kernel=kernel, stride=stride, padding=padding, transposed=transposed, act=act, training=training, direct=False)
+    d = ops._layer_desc(x.shape, 0, weight, spec.k, spec.s, spec.p, spec.transposed)
+    N, IH, IW, C1, cout = d["N"], d["desc"].IH, d["desc"].IW, d["desc"].C1, d["desc"].Cout
     fused1 = bool(has_bn and training and not has_bias and C1 == 1 and ops._caps(d).cin1_bn)
-    state = ops._LayerState(d=d, cfg=cfg, has_bn=has_bn, has_bias=has_bias, dims=(N, IH, IW, C1, 0, cout, d["OH"], d["OW"]),
+    state = ops._LayerState(d=d, spec=spec, has_bn=has_bn, has_bias=has_bias, dims=(N, IH, IW, C1, 0, cout, d["OH"], d["OW"]),
                             xa=xa.reshape(1) if xa.numel() else None, fused1=fused1)
-    ctx = _Ctx((needs[0], False, needs[1], needs[2] and has_bias, needs[3] and has_bn, needs[4] and has_bn, False, False, False, False, False), state,
+    ctx = _Ctx((needs[0], False, needs[1], needs[2] and has_bias, needs[3] and has_bn, needs[4] and has_bn) + (False,) * 7, state,
                (x, None, weight, None if fused1 else (y if has_bn else z), coef if has_bn else None))
     g = ops._ConvBnAct.backward(ctx, dz)
     dev = dz.device
