@@ -7,7 +7,9 @@ each of the nine launch entry points tagged.  Its descriptors are
     at half and quarter size (the two smaller scales of the vision-infused step, configs[3]),
   * the ResNet-18 convs over 1024 frames (7 x 7 stem, the 3 x 3 layers at 56 / 28 / 14 / 7 squared, the 1 x 1 stride-2 shortcuts),
   * sweep rows of tools/conv_routes.py chosen so that every (entry point, family), every P16 mask, every partial geometry and every
-    triple of weight layouts occurs at least three times.
+    triple of weight layouts occurs at least three times,
+  * the Conv1d layers of a teacher-forced WaveNet step (tools/conv_routes.py wavenet_descs: 17-field descriptors, the k = 3 layer dilated
+    and padded on the left only), recorded from the library with the gathered routes.
 Here viai_conv2d_route and the queries must give the recorded answers.  Nothing is launched.
 
 FAMILIES has 38 names: the 37 MFMA / halo / DMA / weight-gradient families plus "direct", the Cin = 1 / Cout = 1 streaming kernels.
@@ -51,6 +53,11 @@ def lib():
     return _lib.load()
 
 
+def _desc17(d):
+    """the 17 descriptor fields of a row: 13 recorded fields mean no dilation and symmetric padding (tools/conv_routes.py desc17)"""
+    return tuple(d) + (0, 0, -1, -1) if len(d) == 13 else tuple(d)
+
+
 def _cin1_without_kernel(d):
     """Cin = 1 outside the streaming kernels' windows and 32 / 64 / 128 output channels: refused since ABI 18 (its entry points used to
     tag "direct" and fail, the weight gradient with a division by zero for Cout < 4)"""
@@ -76,7 +83,7 @@ def test_queries_answer_as_recorded(lib):
     i1, i2 = C.c_int(), C.c_int()
     for r in ROWS:
         d = r[0]
-        c = Conv2dDesc(*d, 0, 0, -1, -1)
+        c = Conv2dDesc(*_desc17(d))
         rc = lib.viai_conv2d_stat_geom(C.byref(c), C.byref(i1), C.byref(i2))
         if _cin1_without_kernel(d):
             assert rc != 0 and lib.viai_conv2d_wgrad_ws_bytes(C.byref(c)) == 0, d
@@ -100,7 +107,7 @@ def test_route_names_the_recorded_kernel(lib):
         d = r[0]
         if len(r) < 21:
             continue
-        c = Conv2dDesc(*d, 0, 0, -1, -1)
+        c = Conv2dDesc(*_desc17(d))
         for i, (rc, n, fam) in enumerate(r[12:21]):
             p, f = tool.pass_form(i, d)
             rn = lib.viai_conv2d_route(C.byref(c), p, f, buf, 64)

@@ -8,13 +8,15 @@ between two builds byte for byte:
 
     python3 tools/conv_routes.py --record OUT.json [--lib PATH/libviai_hip.so]      # full sweep (about 75 k descriptors)
     python3 tools/conv_routes.py --record OUT.json --descs FILE.json                # only the descriptors listed in FILE
+    python3 tools/conv_routes.py --wavenet --merge tests/golden/conv_routes.json    # append the WaveNet Conv1d layers not yet in the table
     python3 tools/conv_routes.py --check-route                                      # viai_conv2d_route == the tag of the launch, every row
     python3 tools/conv_routes.py --time 20 --descs FILE.json [--lib ...]            # host microseconds per entry-point call, no device
 
 The launch part passes null operands: it REFUSES to run when a GPU is present.
 
-Row layout (all integers unless noted):
-    [desc(13), stat_geom(rc, nblk, rows), stat_tiles(rc, th, tw), packed_floats, wgrad_ws_bytes,
+Row layout (all integers unless noted; a descriptor has 13 fields, or 17 where the layer is dilated or padded on one side only:
+FIELDS then dh, dw, ph2, pw2 as include/viai_hip.h defines them):
+    [desc(13 | 17), stat_geom(rc, nblk, rows), stat_tiles(rc, th, tw), packed_floats, wgrad_ws_bytes,
      fwd_f16_ok, dgrad_f16_ok, wgrad_f16_ok, p16_ok, pack_job x 3 (rc, frag, n_out, k_in, s_no, s_ki, nblk),
      launch x 9 (rc, launches, family)]
 launch order = LAUNCHES below; (pass, form) of each for viai_conv2d_route is PASS_FORM.
@@ -54,6 +56,54 @@ def pass_form(i, d):
     if p == 2 and f == FORM_P16:
         f |= wgrad_p16_flags(d) << 2
     return p, f
+
+
+def desc17(d):
+    """the 17 fields of viai_conv2d from a row's descriptor: 13 fields mean no dilation and symmetric padding"""
+    d = tuple(d)
+    if len(d) == 13:
+        return d + (0, 0, -1, -1)
+    assert len(d) == 17, d
+    return d
+
+
+# The Conv1d layers of one teacher-forced WaveNet training step (viai_amd/wavenet.py: conv1d_apply): kh = 1 on (B, 1, T, C) tensors, the
+# k = 3 layer dilated by dw = 2^i and padded on the left only (pw = 2 dw, pw2 = 0), every other layer 1 x 1.  (name, Cin, Cout, k) of every
+# layer of each network width; head2 is the 30-channel output layer as the step runs it, padded to 32 rows (WaveNet.forward_nhwc), and
+# head2_unpadded the same layer without the padding (a forward route only).  Layers of one network, or of two, that share a descriptor
+# (deep: out and skip; 32 -> 32 1 x 1 in small and deep) are recorded once: wavenet_descs() drops the repeats.
+WAVENET_LAYERS = {
+    "full": (("conv", 512, 512, 3), ("cond", 80, 512, 1), ("out", 256, 512, 1), ("skip", 256, 256, 1), ("head1", 256, 256, 1),
+             ("head2", 256, 32, 1), ("head2_unpadded", 256, 30, 1)),
+    "small": (("conv", 64, 64, 3), ("cond", 80, 64, 1), ("out", 32, 64, 1), ("skip", 32, 32, 1), ("head1", 32, 32, 1),
+              ("head2", 32, 32, 1), ("head2_unpadded", 32, 30, 1)),
+    "deep": (("conv", 32, 32, 3), ("cond", 80, 32, 1), ("out", 16, 32, 1), ("skip", 16, 32, 1), ("head1", 32, 32, 1),
+             ("head2", 32, 32, 1), ("head2_unpadded", 32, 30, 1)),
+}
+WAVENET_DILATIONS = (1, 2, 4, 8, 16, 32)
+
+
+def wavenet_desc(N, T, cin, cout, k, d=1, causal=True):
+    """17-field descriptor of a WaveNet Conv1d on (N, 1, T, cin): causal = left padding (k - 1) d, else (k - 1) / 2 * d on both sides"""
+    if k == 1:
+        return (N, 1, T, cin, 0, cout, 1, 1, 1, 1, 0, 0, 0, 1, 1, -1, -1)
+    if causal:
+        return (N, 1, T, cin, 0, cout, 1, k, 1, 1, 0, (k - 1) * d, 0, 1, d, -1, 0)
+    return (N, 1, T, cin, 0, cout, 1, k, 1, 1, 0, (k - 1) // 2 * d, 0, 1, d, -1, -1)
+
+
+def wavenet_descs():
+    """the layers of WAVENET_LAYERS at N = 2: T = 8192 (a training batch of the reference) and T = 64 (the golden's), every dilation of a
+    stack for the k = 3 layer"""
+    out = []
+    for T in (8192, 64):
+        for layers in WAVENET_LAYERS.values():
+            for _name, cin, cout, k in layers:
+                for d in (WAVENET_DILATIONS if k > 1 else (1,)):
+                    desc = wavenet_desc(2, T, cin, cout, k, d)
+                    if desc not in out:
+                        out.append(desc)
+    return out
 
 
 def sweep():
@@ -98,7 +148,7 @@ def record(lib, _lib, descs, launches=True, route=False):
     reset = D(1, 16, 16, 3, 0, 64, 7, 7, 2, 2, 3, 3, 0, 0, 0, -1, -1)
     assert lib.viai_conv2d_dgrad(C.byref(reset), None, None, None, None, None) == 1 and lib.viai_conv2d_last_kernel(buf, 64) == 0
     for d in descs:
-        c = D(*d, 0, 0, -1, -1)
+        c = D(*desc17(d))
         if lib.viai_conv2d_stat_geom(C.byref(c), C.byref(i1), C.byref(i2)) != 0:
             continue                                # not a valid descriptor
         row = [list(d), [0, i1.value, i2.value]]
@@ -157,7 +207,7 @@ def time_calls(lib, _lib, descs, rounds):
     dummy = (C.c_float * 4)()
     amax = C.cast(dummy, C.c_void_p)
     i1, i2 = C.c_int(), C.c_int()
-    cs = [D(*d, 0, 0, -1, -1) for d in descs]
+    cs = [D(*desc17(d)) for d in descs]
     cs = [(c, C.byref(c), amax if c.C2 > 0 else None, wgrad_p16_flags((0, 0, 0, c.C1, c.C2))) for c in cs
           if lib.viai_conv2d_stat_geom(C.byref(c), C.byref(i1), C.byref(i2)) == 0 and not (c.C1 + c.C2 == 1 and c.Cout < 4)]
     calls = {
@@ -194,12 +244,14 @@ def main():
     ap.add_argument("--record", metavar="OUT.json")
     ap.add_argument("--check-route", action="store_true")
     ap.add_argument("--lib", default=None)
-    ap.add_argument("--descs", default=None, help="JSON list of 13-integer descriptors (default: the sweep)")
+    ap.add_argument("--descs", default=None, help="JSON list of 13- or 17-integer descriptors (default: the sweep)")
+    ap.add_argument("--wavenet", action="store_true", help="the descriptors of wavenet_descs() instead of the sweep")
+    ap.add_argument("--merge", metavar="TABLE.json", help="append the recorded rows whose descriptor TABLE does not hold yet; its rows stay as they are")
     a = ap.parse_args()
     lib, _lib = open_lib(a.lib)
     if gpu_present(lib):
         sys.exit("conv_routes.py: a GPU is present; the launch entry points would dereference the null operands. Not run.")
-    descs = [tuple(x) for x in json.load(open(a.descs))] if a.descs else sweep()
+    descs = [tuple(x) for x in json.load(open(a.descs))] if a.descs else wavenet_descs() if a.wavenet else sweep()
     if a.time:
         n, t = time_calls(lib, _lib, list(descs), a.time)
         print("%d descriptors, us per call: %s" % (n, json.dumps(t)))
@@ -207,8 +259,15 @@ def main():
     rows, bad = record(lib, _lib, descs, route=a.check_route)
     fams = sorted({r[-1 - k][2] for r in rows if len(r) > 15 for k in range(9)} - {""})
     print("%d descriptors, %d kernel families: %s" % (len(rows), len(fams), " ".join(fams)))
-    if a.record:
-        with open(a.record, "w") as f:
+    out = a.record
+    if a.merge:
+        old = json.load(open(a.merge))
+        have = {tuple(r[0]) for r in old}
+        new = [r for r in rows if tuple(r[0]) not in have]
+        print("%s: %d rows, %d appended" % (a.merge, len(old), len(new)))
+        rows, out = old + new, a.merge
+    if out:
+        with open(out, "w") as f:
             f.write("[\n" + ",\n".join(json.dumps(r, separators=(",", ":")) for r in rows) + "\n]\n")
     if a.check_route:
         print("route mismatches: %d" % bad)

@@ -129,10 +129,16 @@ __global__ __launch_bounds__(256) void outer_bwd_part_kernel(const float* __rest
     for (int g0 = 0; g0 < CG; g0 += 256) {
         const int cgw = min(256, CG - g0), pg = 256 / cgw, cg = tid % cgw, pl = tid / cgw;
         f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+        // rows in runs of 32 per lane, each run summed on its own: a lane's fp32 error stays that of two short sums (C > 1024 leaves one lane
+        // per column group, up to 1024 rows in a single accumulator: 4.8 x the error of torch's fp32 column sum at 1000 rows)
         if (pl < pg)
-            for (long r = row0 + pl; r < row1; r += pg) {
-                f32x4 g = *reinterpret_cast<const f32x4*>(dy + r * C + (g0 + cg) * 4);
-                s1 += g * x[r]; s2 += g;
+            for (long r = row0 + pl; r < row1;) {
+                f32x4 p1 = {0.f, 0.f, 0.f, 0.f}, p2 = {0.f, 0.f, 0.f, 0.f};
+                for (int u = 0; u < 32 && r < row1; ++u, r += pg) {
+                    f32x4 g = *reinterpret_cast<const f32x4*>(dy + r * C + (g0 + cg) * 4);
+                    p1 += g * x[r]; p2 += g;
+                }
+                s1 += p1; s2 += p2;
             }
         r1[tid] = s1; r2[tid] = s2;
         __syncthreads();
