@@ -407,6 +407,39 @@ int viai_class_embed_bwd(const float* dh, const int* classes, float* part, float
  * with a load of `*step` in front of its address arithmetic (a full memory round trip at these grid sizes).  `step` is not touched.
  * wavenet.py:237-364 incremental_forward's loop body, n_steps at a time.                                                         */
 int viai_wavenet_synth_run(const viai_wn_synth* s, int t0, int n_steps, void* stream);
+/* The same two calls with the teacher-forced steps chosen per stream and step (additive to ABI v20).  wavenet.py:322-327 forces a PREFIX, common
+ * to the batch: test_inputs is used while t < n_test.  Here a mask `forced` (B, T) uint8 in device memory travels with test inputs that cover all
+ * T steps (n_test == T is required: test_inputs (B, T) for the scalar network, test_classes (B, T) and / or test_inputs (B, T, K) for the one-hot
+ * network), and the INPUT of step t of stream b is
+ *     forced[b][t] != 0:  the given input -- test_inputs[b][t], or class test_classes[b][t] / row test_inputs[b][t]
+ *     otherwise:          the previous output (out / classes / yhat_dbg at t - 1), or at t == 0 the start value (0.0 / init_rows / init_class).
+ * Outputs are unchanged: step t writes the model's own sample, class or row at t whether or not its input was forced (wavenet.py:326-356).  A
+ * step the mask does not force may hold anything in the test inputs.  forced == NULL is the prefix rule, i.e. viai_wavenet_synth_run / _step
+ * themselves.  One-hot network: a step is in class form only if EVERY stream's input is a class; where the streams differ (one forced from dense
+ * rows, one fed back as a class) the step takes the dense first conv and the class streams gather their weight row there.  The plain chain, the
+ * fused chain (s->fused) and the device-side time index (_step_forced, for a captured graph) all take the mask; the pipelined form
+ * (viai_wn_pipe_run) does not -- a caller with a mask uses these.                                                                              */
+int viai_wavenet_synth_step_forced(const viai_wn_synth* s, const unsigned char* forced, void* stream);
+int viai_wavenet_synth_run_forced(const viai_wn_synth* s, const unsigned char* forced, int t0, int n_steps, void* stream);
+
+/* ---- inpainting a gap in a waveform (csrc/wn_inpaint.hip; additive to ABI v20) ----
+ * Only the receptive field R in front of a gap and the gap itself need the sample-by-sample loop: the R known samples, teacher-forced, bring
+ * every dilated conv's ring buffer (conv.py:17-46) to the state it has after the whole clip, and the gap runs free (wavenet.py:322-327).
+ * viai_wn_window_gather cuts one window per stream out of a clip: window position t of stream b is clip time w[b] + t (w[b] = gap start - R, may
+ * be negative), t < L = R + the longest gap.
+ *   inputs   wav (B, n) floats and / or classes (B, n) int32 (either may be NULL, not both) -> x_out (B, L) / cls_out (B, L)
+ *   cond     (B, n, cin) up-sampled conditioning (wavenet.py:291-299), or NULL -> cond_out (B, L, cin); cin % 4 == 0, 16-byte rows
+ *   forced   (B, L) uint8: forced[b][t] = !(R <= t < R + len[b]) -- the steps behind a short gap are forced again (their outputs are not used)
+ * Times before 0 or at and beyond n read as silence, the start-up state of wavenet.py:305-312: 0.0, class `silence_class` (127 at mu = 255) and a
+ * zero conditioning row.  w, len: B int32 in device memory.                                                                                    */
+int viai_wn_window_gather(const float* wav, const int* classes, const float* cond, const int* w, const int* len, float* x_out, int* cls_out,
+                          float* cond_out, unsigned char* forced, int B, int n, int L, int R, int cin, int silence_class, void* stream);
+/* out (B, n): out[b][i] = wav[b][i] outside the gap [g0[b], g0[b] + len[b]); inside, g = gen[b][R + i - g0[b]] with gen (B, L) the window's
+ * generated samples.  fade > 0 blends the last `fade` samples of the gap linearly from generated to original (for callers that do have the
+ * original there, as in evaluation): with j = i - (g0[b] + len[b] - fade) >= 0 and a = (j + 1) / (fade + 1),
+ *     out[b][i] = g + a * (wav[b][i] - g)      in fp32, every operation rounded on its own.
+ * fade == 0 is an exact copy on both sides.  g0, len: B int32 in device memory; out must not alias wav.                                         */
+int viai_wn_splice(const float* wav, const float* gen, const int* g0, const int* len, float* out, int B, int n, int L, int R, int fade, void* stream);
 
 /* Incremental synthesis as ONE persistent launch (ABI v16, csrc/wavenet_pipe.hip): a weight-stationary pipeline for the reference-size
  * network (24 layers, 512 residual / 512 gate / 256 skip channels, 80 conditioning channels, 30 outputs, no global conditioning).  Every

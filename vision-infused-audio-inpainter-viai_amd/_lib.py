@@ -156,6 +156,10 @@ SIGNATURES = {
     "viai_mol_sample": (_I, [_P, _P, _P, _P, _L, _I, _I, _F, _P]),
     "viai_wavenet_synth_step": (_I, [C.POINTER(WnSynth), _P]),
     "viai_wavenet_synth_run": (_I, [C.POINTER(WnSynth), _I, _I, _P]),
+    "viai_wavenet_synth_step_forced": (_I, [C.POINTER(WnSynth), _P, _P]),
+    "viai_wavenet_synth_run_forced": (_I, [C.POINTER(WnSynth), _P, _I, _I, _P]),
+    "viai_wn_window_gather": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "viai_wn_splice": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "viai_wn_categorical_ok": (_I, [C.POINTER(WnSynth)]),
     "viai_mulaw_decode": (_I, [_P, _P, _L, _I, _P]),
     "viai_mulaw_quantize": (_I, [_P, _P, _L, _I, _P]),

@@ -756,6 +756,19 @@ namespace {
 
 constexpr int WN_MAXB = 8;
 
+// A stream's arithmetic must not depend on how many streams travel with it: the kernels below are templates over the stream count NB, and with
+// floating-point contraction left to the compiler each instantiation fused another subset of the products into its sums (it packs the streams
+// pairwise: wn_out_kernel<1> had no fused multiply-add, <2> had), so stream b of a 4-stream run differed in the last bits from the 1-stream run
+// on the same inputs.  WN_STRICT_FP, first statement of every NB-templated kernel, switches contraction off there: every product and sum is
+// rounded on its own, in source order, whatever NB is.
+#define WN_STRICT_FP _Pragma("clang fp contract(off)")
+
+// Is the input of time step t of stream b given (teacher-forced)?  Without a mask: the common prefix t < n_test (wavenet.py:322-323).  With a
+// mask `forced` (B, T) uint8 (viai_wavenet_synth_run_forced; the test inputs then cover all T steps, n_test == T): the mask's entry.
+__device__ __forceinline__ bool wn_forced(const unsigned char* __restrict__ forced, int n_test, int T, int t, int b) {
+    return forced != nullptr ? forced[(size_t)b * T + t] != 0 : t < n_test;
+}
+
 // x0[b][:] = cur[b] * w_first + b_first -> ring0[slot(t)];  cur = test_inputs[t] | out[t-1] | 0
 // ONE block.  The time index comes either by value (t_arg >= 0: viai_wavenet_synth_run, the host loop knows it) or from device memory
 // (t_arg < 0: viai_wavenet_synth_step, replayable from a hipGraph): there this kernel also advances it once all of its threads have
@@ -764,12 +777,13 @@ constexpr int WN_MAXB = 8;
 // every address computation of every kernel, which is why the by-value path exists.
 __global__ __launch_bounds__(256) void wn_first_kernel(const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ test_inputs,
                                                        int n_test, const float* __restrict__ out, float* __restrict__ ring, int ring_len,
-                                                       int* __restrict__ step, int t_arg, int B, int C, int T) {
+                                                       int* __restrict__ step, int t_arg, int B, int C, int T,
+                                                       const unsigned char* __restrict__ forced) {
     const int t = t_arg >= 0 ? t_arg : *step;
     const int slot = t % ring_len;
     for (int i = threadIdx.x; i < B * C; i += 256) {
         int b = i / C, c = i % C;
-        float cur = (t < n_test) ? test_inputs[(size_t)b * n_test + t] : (t > 0 ? out[(size_t)b * T + t - 1] : 0.f);
+        float cur = wn_forced(forced, n_test, T, t, b) ? test_inputs[(size_t)b * n_test + t] : (t > 0 ? out[(size_t)b * T + t - 1] : 0.f);
         ring[((size_t)b * ring_len + slot) * C + c] = cur * w[c] + bias[c];
     }
     if (t_arg < 0) {
@@ -787,6 +801,7 @@ __global__ __launch_bounds__(256) void wn_gate_kernel(const float* __restrict__ 
                                                       const float* __restrict__ bconv, const float* __restrict__ wc, const float* __restrict__ bc,
                                                       const float* __restrict__ cond, const float* __restrict__ gadd, float* __restrict__ z,
                                                       const int* __restrict__ step, int t_arg, int C, int H, int cin, int T) {
+    WN_STRICT_FP
     __shared__ float red[2 * NB][260];
     const int t = t_arg >= 0 ? t_arg : *step - 1;
     const int h = blockIdx.x, tid = threadIdx.x;
@@ -859,6 +874,7 @@ __global__ __launch_bounds__(256) void wn_out_kernel(const float* __restrict__ z
                                                      const float* __restrict__ wskip, const float* __restrict__ bskip,
                                                      const float* __restrict__ ring, int ring_len, float* __restrict__ next_ring, int next_len,
                                                      float* __restrict__ skips, int first, const int* __restrict__ step, int t_arg, int C, int H, int S) {
+    WN_STRICT_FP
     const int t = t_arg >= 0 ? t_arg : *step - 1;
     const int o = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (o >= C + S) return;
@@ -1013,27 +1029,41 @@ __global__ __launch_bounds__(256) void wn_head_generic_kernel(const float* __res
 // writes z_l while its B blocks still read z_{l-1}).  Reassociation only: sums agree with the plain form to fp32 rounding.
 // ---- categorical network (ABI 19): where the input of a time step comes from (wavenet.py:322-327), shared by both chain forms --------------
 // Two forms of the first conv (wavenet.py:116-119, Conv1d1x1(K, C)): the input of stream b is a CLASS k -> x0 = w_t[k] + bias, one contiguous
-// row of the transposed weight; or a DENSE row of K floats -> x0[c] = w[c] . row + bias[c].  The form depends on t and the descriptor only,
-// never on the stream, so every branch on it is uniform over the grid.
+// row of the transposed weight; or a DENSE row of K floats -> x0[c] = w[c] . row + bias[c].  The form of a STEP depends on t, the descriptor
+// and (where there is one) the mask of forced steps, never on the block, so every branch on it is uniform over the grid.
 struct WnCatIn {
     const float* w_t; const float* w;              // [K][C] / [C][K]
     const int* test_classes; const float* test_rows; const float* init_rows;
     const int* classes; const float* rows;         // what the previous time steps put out: (B, T) / (B, T, K)
     int n_test, init_class, quantize, K, T;
+    const unsigned char* forced;                   // optional (B, T) mask of the teacher-forced steps (wn_forced)
 };
 
-__device__ __forceinline__ bool wn_cat_class_form(const WnCatIn& in, int t) {
-    if (t < in.n_test) return in.test_classes != nullptr;
+// the form of stream b's input at step t; without a mask it is the same for every stream
+__device__ __forceinline__ bool wn_cat_class_form_of(const WnCatIn& in, int t, int b) {
+    if (wn_forced(in.forced, in.n_test, in.T, t, b)) return in.test_classes != nullptr;
     if (t > 0) return in.quantize != 0;
     return in.init_rows == nullptr;
 }
+// the form of the STEP: class form only if every stream's input is a class.  With a mask the streams may differ (one forced from dense rows,
+// one fed back as a class): such a step takes the dense path, where a class stream still gathers its row (wn_cat_first_kernel).  The answer
+// depends on t, the descriptor and the mask only, so every branch on it is uniform over the grid.
+template <int NB>
+__device__ __forceinline__ bool wn_cat_class_form(const WnCatIn& in, int t) {
+    if (in.forced == nullptr) return wn_cat_class_form_of(in, t, 0);
+    bool all = true;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) all = all && wn_cat_class_form_of(in, t, b);
+    return all;
+}
 __device__ __forceinline__ int wn_cat_class(const WnCatIn& in, int t, int b) {
-    const int k = t < in.n_test ? in.test_classes[(size_t)b * in.n_test + t] : (t > 0 ? in.classes[(size_t)b * in.T + t - 1] : in.init_class);
+    const int k = wn_forced(in.forced, in.n_test, in.T, t, b) ? in.test_classes[(size_t)b * in.n_test + t]
+                                                              : (t > 0 ? in.classes[(size_t)b * in.T + t - 1] : in.init_class);
     return min(max(k, 0), in.K - 1);               // a class from outside (test_classes) never indexes past the weight
 }
 __device__ __forceinline__ const float* wn_cat_row(const WnCatIn& in, int t, int b) {
-    return t < in.n_test ? in.test_rows + ((size_t)b * in.n_test + t) * in.K
-                         : (t > 0 ? in.rows + ((size_t)b * in.T + t - 1) * in.K : in.init_rows + (size_t)b * in.K);
+    return wn_forced(in.forced, in.n_test, in.T, t, b) ? in.test_rows + ((size_t)b * in.n_test + t) * in.K
+                                                       : (t > 0 ? in.rows + ((size_t)b * in.T + t - 1) * in.K : in.init_rows + (size_t)b * in.K);
 }
 
 struct WnStage {
@@ -1047,6 +1077,7 @@ struct WnStage {
     const float* w_out; const float* b_out; const float* w_skip; const float* b_skip;                      // layer l - 1 (B blocks)
     float* ring_w; float* skips; int first_skip;
     const int* step; int t_arg, l, C, H, S, cin, T, B;
+    const unsigned char* forced;                   // stage 0 of the scalar-input network: wn_forced
 };
 
 __global__ void wn_tick_kernel(int* step) { *step += 1; }
@@ -1055,6 +1086,7 @@ __global__ void wn_tick_kernel(int* step) { *step += 1; }
 // wn_cat_first_kernel does in a launch of its own in front of this stage (ring slot t), and stage 0 reads its current tap from there.
 template <int NB, bool CAT = false>
 __global__ __launch_bounds__(256) void wn_stage_kernel(const WnStage a) {
+    WN_STRICT_FP
     __shared__ float red[2 * NB][260];
     const int t = a.t_arg >= 0 ? a.t_arg : *a.step - 1;
     const int tid = threadIdx.x, C = a.C, H = a.H;
@@ -1062,7 +1094,7 @@ __global__ __launch_bounds__(256) void wn_stage_kernel(const WnStage a) {
         // ---------------------------------------------------------------- B: what layer l - 1 still owes (or the first conv)
         const int bid = blockIdx.x - H;
         if (CAT && a.l == 0) {
-            if (wn_cat_class_form(a.cat, t))
+            if (wn_cat_class_form<NB>(a.cat, t))
                 for (int i = tid; i < NB * C; i += 256) {
                     const int b = i / C, c = i - b * C;
                     a.ring_w[((size_t)b * a.ring_len + (t % a.ring_len)) * C + c] = a.cat.w_t[(size_t)wn_cat_class(a.cat, t, b) * C + c] + a.b_first[c];
@@ -1072,7 +1104,7 @@ __global__ __launch_bounds__(256) void wn_stage_kernel(const WnStage a) {
         if (a.l == 0) {
             for (int i = tid; i < NB * C; i += 256) {
                 const int b = i / C, c = i - b * C;
-                const float cur = (t < a.n_test) ? a.test_inputs[(size_t)b * a.n_test + t] : (t > 0 ? a.out[(size_t)b * a.T + t - 1] : 0.f);
+                const float cur = wn_forced(a.forced, a.n_test, a.T, t, b) ? a.test_inputs[(size_t)b * a.n_test + t] : (t > 0 ? a.out[(size_t)b * a.T + t - 1] : 0.f);
                 a.ring_w[((size_t)b * a.ring_len + (t % a.ring_len)) * C + c] = cur * a.w_first[c] + a.b_first[c];
             }
             return;
@@ -1138,7 +1170,7 @@ __global__ __launch_bounds__(256) void wn_stage_kernel(const WnStage a) {
             } else if (k < 3 * C) {                                 // current tap
                 const int ci = k - 2 * C;
                 if (CAT && a.l == 0) {                              // x_0(t) of the categorical network
-                    if (wn_cat_class_form(a.cat, t)) {
+                    if (wn_cat_class_form<NB>(a.cat, t)) {
                         const f32x4 bf = *reinterpret_cast<const f32x4*>(a.b_first + ci);
 #pragma unroll
                         for (int b = 0; b < NB; ++b) x[b] = *reinterpret_cast<const f32x4*>(a.cat.w_t + (size_t)wn_cat_class(a.cat, t, b) * C + ci) + bf;
@@ -1151,7 +1183,7 @@ __global__ __launch_bounds__(256) void wn_stage_kernel(const WnStage a) {
                     const f32x4 wf = *reinterpret_cast<const f32x4*>(a.w_first + ci), bf = *reinterpret_cast<const f32x4*>(a.b_first + ci);
 #pragma unroll
                     for (int b = 0; b < NB; ++b) {
-                        const float cur = (t < a.n_test) ? a.test_inputs[(size_t)b * a.n_test + t] : (t > 0 ? a.out[(size_t)b * a.T + t - 1] : 0.f);
+                        const float cur = wn_forced(a.forced, a.n_test, a.T, t, b) ? a.test_inputs[(size_t)b * a.n_test + t] : (t > 0 ? a.out[(size_t)b * a.T + t - 1] : 0.f);
                         x[b] = cur * wf + bf;
                     }
                 } else {                                            // x_{l-1}(t), against sqrt(.5) Wc^2
@@ -1294,6 +1326,7 @@ __global__ __launch_bounds__(1024) void wn_head_fused_kernel(const float* __rest
 template <int NB>
 __global__ __launch_bounds__(256) void wn_head_rows_kernel(const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ x, int K,
                                                            float* __restrict__ out, int nrows, int mode, int first_skip) {
+    WN_STRICT_FP
     const int o = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (o >= nrows) return;
     float acc[NB];
@@ -1359,11 +1392,12 @@ __global__ __launch_bounds__(256) void wn_head_sample_kernel(const float* __rest
 template <int NB>
 __global__ __launch_bounds__(256) void wn_cat_first_kernel(const WnCatIn in, const float* __restrict__ bias, float* __restrict__ ring, int ring_len,
                                                            const int* __restrict__ step, int t_arg, int C, int dense_only) {
+    WN_STRICT_FP
     const int t = t_arg >= 0 ? t_arg : *step - 1;
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= C) return;
     const int slot = t % ring_len;
-    if (wn_cat_class_form(in, t)) {
+    if (wn_cat_class_form<NB>(in, t)) {
         if (!dense_only && lane < NB) ring[((size_t)lane * ring_len + slot) * C + c] = in.w_t[(size_t)wn_cat_class(in, t, lane) * C + c] + bias[c];
         return;
     }
@@ -1375,13 +1409,15 @@ __global__ __launch_bounds__(256) void wn_cat_first_kernel(const WnCatIn in, con
         const f32x4 wv = *reinterpret_cast<const f32x4*>(in.w + (size_t)c * in.K + k);
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
+            if (in.forced != nullptr && wn_cat_class_form_of(in, t, b)) continue;      // a class stream in a mixed step: gathered below
             const f32x4 xv = *reinterpret_cast<const f32x4*>(wn_cat_row(in, t, b) + k);
             acc[b] += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
         }
     }
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-        const float v = wave_sum_dpp(acc[b]);
+        float v = wave_sum_dpp(acc[b]);
+        if (in.forced != nullptr && wn_cat_class_form_of(in, t, b)) v = in.w_t[(size_t)wn_cat_class(in, t, b) * C + c];
         if (lane == 0) ring[((size_t)b * ring_len + slot) * C + c] = v + bv;
     }
 }
@@ -1390,6 +1426,7 @@ __global__ __launch_bounds__(256) void wn_cat_first_kernel(const WnCatIn in, con
 template <int NB>
 __global__ __launch_bounds__(256) void wn_cat_rows_kernel(const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ x, int K,
                                                           float* __restrict__ out, int nrows, int relu_out) {
+    WN_STRICT_FP
     const int o = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (o >= nrows) return;
     const float bv = bias[o];
@@ -1472,16 +1509,20 @@ __global__ __launch_bounds__(256) void mulaw_decode_kernel(const int* __restrict
     }
 }
 
-WnCatIn wn_cat_in(const viai_wn_synth* s) {
+WnCatIn wn_cat_in(const viai_wn_synth* s, const unsigned char* forced) {
     WnCatIn in{};
+    in.forced = forced;
     in.w_t = s->w_first_t; in.w = s->w_first; in.test_classes = s->test_classes; in.test_rows = s->test_inputs; in.init_rows = s->init_rows;
     in.classes = s->classes; in.rows = s->yhat_dbg; in.n_test = s->n_test; in.init_class = s->init_class; in.quantize = s->cat_quantize;
     in.K = s->out_ch; in.T = s->T;
     return in;
 }
 
-// host copy of wn_cat_class_form; t < 0 (time index on the device): "may a dense step occur at all"
-bool wn_cat_dense_at(const viai_wn_synth* s, int t) {
+// host copy of wn_cat_class_form; t < 0 (time index on the device): "may a dense step occur at all".  With a mask of forced steps, which lives
+// in device memory, the host can only say whether a step MAY be dense: a forced one (dense test rows), a fed-back one (no quantize) or a
+// free first step from init_rows.  A launch this lets through for a step that turns out to be all classes returns at once.
+bool wn_cat_dense_at(const viai_wn_synth* s, int t, const unsigned char* forced) {
+    if (forced != nullptr) return s->test_classes == nullptr || !s->cat_quantize || (t <= 0 && s->init_rows != nullptr);
     if (t < 0) return (s->n_test > 0 && s->test_classes == nullptr) || !s->cat_quantize || (s->n_test == 0 && s->init_rows != nullptr);
     if (t < s->n_test) return s->test_classes == nullptr;
     if (t > 0) return !s->cat_quantize;
@@ -1509,13 +1550,13 @@ bool wn_fused_ok(const viai_wn_synth* s) {
 }
 
 template <int NB>
-int wn_step_fused_impl(const viai_wn_synth* s, int t_arg, hipStream_t st) {
+int wn_step_fused_impl(const viai_wn_synth* s, int t_arg, hipStream_t st, const unsigned char* forced) {
     const int C = s->C, H = s->G / 2, S = s->S, n = s->n_layers;
     const viai_wn_layer* L = s->layers;
     if (t_arg < 0) VIAI_LAUNCH(wn_tick_kernel, dim3(1), dim3(1), 0, st, s->step);
     const bool cat = s->categorical != 0;
-    if (cat && wn_cat_dense_at(s, t_arg))
-        VIAI_LAUNCH(wn_cat_first_kernel<NB>, dim3((C + 3) / 4), dim3(256), 0, st, wn_cat_in(s), s->b_first, L[0].ring, L[0].ring_len, s->step, t_arg, C, 1);
+    if (cat && wn_cat_dense_at(s, t_arg, forced))
+        VIAI_LAUNCH(wn_cat_first_kernel<NB>, dim3((C + 3) / 4), dim3(256), 0, st, wn_cat_in(s, forced), s->b_first, L[0].ring, L[0].ring_len, s->step, t_arg, C, 1);
     float* zb[2] = {s->z, s->z2};
     for (int l = 0; l < n; ++l) {
         WnStage a{};
@@ -1529,10 +1570,10 @@ int wn_step_fused_impl(const viai_wn_synth* s, int t_arg, hipStream_t st) {
             a.w_out = L[l - 1].w_out; a.b_out = L[l - 1].b_out; a.w_skip = L[l - 1].w_skip; a.b_skip = L[l - 1].b_skip;
             a.first_skip = (l == 1) ? 1 : 0;
         }
-        a.step = s->step; a.t_arg = t_arg; a.l = l; a.C = C; a.H = H; a.S = S; a.cin = s->cin; a.T = s->T; a.B = s->B;
+        a.step = s->step; a.t_arg = t_arg; a.l = l; a.C = C; a.H = H; a.S = S; a.cin = s->cin; a.T = s->T; a.B = s->B; a.forced = forced;
         const int nb = H + (l == 0 ? 1 : (C + S + 3) / 4);
         if (cat && l == 0) {
-            a.cat = wn_cat_in(s);
+            a.cat = wn_cat_in(s, forced);
             VIAI_LAUNCH((wn_stage_kernel<NB, true>), dim3(nb), dim3(256), 0, st, a);
         } else {
             VIAI_LAUNCH(wn_stage_kernel<NB>, dim3(nb), dim3(256), 0, st, a);
@@ -1559,15 +1600,15 @@ int wn_step_fused_impl(const viai_wn_synth* s, int t_arg, hipStream_t st) {
 }
 
 template <int NB>
-int wn_step_impl(const viai_wn_synth* s, int t_arg, hipStream_t st) {
+int wn_step_impl(const viai_wn_synth* s, int t_arg, hipStream_t st, const unsigned char* forced) {
     const int C = s->C, H = s->G / 2, S = s->S;
     const viai_wn_layer* L = s->layers;
     if (s->categorical) {                          // several blocks: the time index is advanced by a launch of its own, as in the fused form
         if (t_arg < 0) VIAI_LAUNCH(wn_tick_kernel, dim3(1), dim3(1), 0, st, s->step);
-        VIAI_LAUNCH(wn_cat_first_kernel<NB>, dim3((C + 3) / 4), dim3(256), 0, st, wn_cat_in(s), s->b_first, L[0].ring, L[0].ring_len, s->step, t_arg, C, 0);
+        VIAI_LAUNCH(wn_cat_first_kernel<NB>, dim3((C + 3) / 4), dim3(256), 0, st, wn_cat_in(s, forced), s->b_first, L[0].ring, L[0].ring_len, s->step, t_arg, C, 0);
     } else
     VIAI_LAUNCH(wn_first_kernel, dim3(1), dim3(256), 0, st, s->w_first, s->b_first, s->test_inputs, s->n_test, s->out,
-                L[0].ring, L[0].ring_len, s->step, t_arg, s->B, C, s->T);
+                L[0].ring, L[0].ring_len, s->step, t_arg, s->B, C, s->T, forced);
     for (int l = 0; l < s->n_layers; ++l) {
         VIAI_LAUNCH(wn_gate_kernel<NB>, dim3(H), dim3(256), 0, st, L[l].ring, L[l].ring_len, L[l].dilation, L[l].w_conv, L[l].b_conv,
                     L[l].w_c, L[l].b_c, s->cond, L[l].g_add, s->z, s->step, t_arg, C, H, s->cin, s->T);
@@ -1599,23 +1640,29 @@ bool wn_valid(const viai_wn_synth* s) {
     return true;
 }
 
-int wn_step(const viai_wn_synth* s, int t_arg, hipStream_t st) {
+int wn_step(const viai_wn_synth* s, int t_arg, hipStream_t st, const unsigned char* forced = nullptr) {
     if (wn_fused_ok(s)) {
         switch (s->B) {
-        case 1: return wn_step_fused_impl<1>(s, t_arg, st);
-        case 2: return wn_step_fused_impl<2>(s, t_arg, st);
-        case 4: return wn_step_fused_impl<4>(s, t_arg, st);
-        case 8: return wn_step_fused_impl<8>(s, t_arg, st);
+        case 1: return wn_step_fused_impl<1>(s, t_arg, st, forced);
+        case 2: return wn_step_fused_impl<2>(s, t_arg, st, forced);
+        case 4: return wn_step_fused_impl<4>(s, t_arg, st, forced);
+        case 8: return wn_step_fused_impl<8>(s, t_arg, st, forced);
         default: return (int)hipErrorInvalidValue;
         }
     }
     switch (s->B) {
-    case 1: return wn_step_impl<1>(s, t_arg, st);
-    case 2: return wn_step_impl<2>(s, t_arg, st);
-    case 4: return wn_step_impl<4>(s, t_arg, st);
-    case 8: return wn_step_impl<8>(s, t_arg, st);
+    case 1: return wn_step_impl<1>(s, t_arg, st, forced);
+    case 2: return wn_step_impl<2>(s, t_arg, st, forced);
+    case 4: return wn_step_impl<4>(s, t_arg, st, forced);
+    case 8: return wn_step_impl<8>(s, t_arg, st, forced);
     default: return (int)hipErrorInvalidValue;
     }
+}
+
+// a mask needs given inputs at all T steps (wn_valid has checked that the one-hot network has classes or rows where n_test > 0)
+bool wn_forced_valid(const viai_wn_synth* s, const unsigned char* forced) {
+    if (forced == nullptr) return true;
+    return s->T >= 1 && s->n_test == s->T && (s->categorical || s->test_inputs != nullptr);
 }
 
 }  // namespace
@@ -1646,6 +1693,20 @@ extern "C" int viai_wavenet_synth_run(const viai_wn_synth* s, int t0, int n_step
     if (!wn_valid(s) || t0 < 0 || n_steps < 0 || t0 + n_steps > s->T) return (int)hipErrorInvalidValue;
     for (int t = t0; t < t0 + n_steps; ++t) {
         const int e = wn_step(s, t, (hipStream_t)stream);
+        if (e != 0) return e;
+    }
+    return 0;
+}
+
+extern "C" int viai_wavenet_synth_step_forced(const viai_wn_synth* s, const unsigned char* forced, void* stream) {
+    if (!wn_valid(s) || !wn_forced_valid(s, forced)) return (int)hipErrorInvalidValue;
+    return wn_step(s, -1, (hipStream_t)stream, forced);
+}
+
+extern "C" int viai_wavenet_synth_run_forced(const viai_wn_synth* s, const unsigned char* forced, int t0, int n_steps, void* stream) {
+    if (!wn_valid(s) || !wn_forced_valid(s, forced) || t0 < 0 || n_steps < 0 || t0 + n_steps > s->T) return (int)hipErrorInvalidValue;
+    for (int t = t0; t < t0 + n_steps; ++t) {
+        const int e = wn_step(s, t, (hipStream_t)stream, forced);
         if (e != 0) return e;
     }
     return 0;

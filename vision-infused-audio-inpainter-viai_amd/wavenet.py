@@ -13,7 +13,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import _lib, ops, wavenet_synth
+from . import _lib, ops, wavenet_inpaint, wavenet_synth
 from .ops import ACT_NONE, ACT_RELU, _c, _ptr, _require, _stream
 
 
@@ -425,6 +425,17 @@ def mulaw_quantize(x, mu=255):
     return out.long()
 
 
+def inpaint_waveform(net, wav, c, gap_start, gap_len, uniforms=None, fade=0, return_window=False):
+    """Fill one gap per stream of a waveform with the vocoder `net`: the receptive field in front of every gap is teacher-forced, the gap runs
+    free, everything else is copied (viai_amd/wavenet_inpaint.py, documented there)."""
+    return wavenet_inpaint.inpaint_waveform(net, wav, c, gap_start, gap_len, uniforms, fade, return_window)
+
+
+def gaps_from_mask(mask):
+    """(B, 1, 1, frames) time mask of `model.make_time_mask` (1 = known, 0 = gap) -> (gap_start, gap_len), two (B,) int64 tensors in frames."""
+    return wavenet_inpaint.gaps_from_mask(mask)
+
+
 # ----------------------------------------------------------------------------- modules
 def _wn(m, on):
     return nn.utils.weight_norm(m) if on else m
@@ -620,7 +631,7 @@ class WaveNet(nn.Module):
     @torch.no_grad()
     def incremental_forward(self, initial_input=None, c=None, g=None, T=100, test_inputs=None, tqdm=lambda x: x, softmax=True,
                             quantize=True, log_scale_min=-7.0, uniforms=None, use_graph=False, return_logits=False, timing=None,
-                            return_classes=False, input_form="auto"):
+                            return_classes=False, input_form="auto", forced=None, c_upsampled=False):
         """Sample-by-sample synthesis (wavenet.py:237-364), both configurations of the reference.
 
         scalar_input=False (one-hot mu-law input, softmax over K = out_channels classes; chain forms only): returns (B, K, T) like the reference --
@@ -631,6 +642,13 @@ class WaveNet(nn.Module):
         `return_classes=True` (with quantize): the (B, T) int64 classes, the (B, K, T) one-hot tensor is never formed.  `test_inputs` /
         `initial_input` in either layout, (B, K, n) or (B, n, K); teacher-forced rows that are exactly one-hot go through the class form of
         the first conv (a row gather), anything else -- or everything, with input_form="dense" -- through the dense form (a K-long product).
+        Integer `test_inputs` (B, n) are the classes themselves (class form, no one-hot tensor).
+
+        `forced=` (B, T) bool or uint8 (both networks): which steps are teacher-forced, per stream -- the reference forces a prefix common to
+        the batch (wavenet.py:322-327).  The input of step t of stream b is test_inputs[b, t] where forced[b, t], else the previous output
+        (at t = 0 the start value); every step still returns the model's own output.  The number of steps is the mask's, `test_inputs` must
+        have exactly that length, and what it holds at steps that are not forced is never read.  Chain forms only (the pipelined form is not
+        taken).  `c_upsampled=True`: `c` is already at the sample rate, (B, cin, T), and the up-sampling stack is skipped.
 
         scalar_input=True (mixture of logistics):
 
@@ -641,7 +659,7 @@ class WaveNet(nn.Module):
         `timing={"warmup": W}` (bench.py): the first W time steps run untimed, the remaining T - W are bracketed by device
         synchronisations and reported as timing["ms"] / timing["steps"] (set-up -- weight norm, linearised weights -- excluded)."""
         return wavenet_synth.incremental_forward(self, initial_input, c, g, T, test_inputs, tqdm, softmax, quantize, log_scale_min, uniforms, use_graph,
-                                                 return_logits, timing, return_classes, input_form)
+                                                 return_logits, timing, return_classes, input_form, forced, c_upsampled)
 
     def make_generation_fast_(self):
         def rm(m):

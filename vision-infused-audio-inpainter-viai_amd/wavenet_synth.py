@@ -1,9 +1,10 @@
 """Host path of `WaveNet.incremental_forward` (sample-by-sample synthesis, wavenet.py:237-364 of the reference), in the order a call goes through it:
 
-  _resolve_inputs   argument checks, normalised inputs, conditioning up-sample, the sampler's uniforms      -> _Inputs
+  _resolve_inputs   argument checks, normalised inputs, the mask of forced steps, conditioning up-sample, the sampler's uniforms -> _Inputs
   _synth_weights    every holder module's effective weight, once, in every layout the launch forms read    -> _Weights
   _SynthState       owns every tensor the C descriptor (`_lib.WnSynth` / `_lib.WnLayer`) points to, and builds the descriptor
-  _synth_form       which launch form runs: "pipe" (csrc/wavenet_pipe.hip), "graph" or "chain" (csrc/wavenet.hip) -- a pure function
+  _synth_form       which launch form runs: "pipe" (csrc/wavenet_pipe.hip), "graph" or "chain" (csrc/wavenet.hip) -- a pure function; a call with a
+                    mask of forced steps takes the chain forms (the pipelined kernel knows the prefix rule only)
   _run_pipe / _run_graph / _run_chain
 
 The kernels, the descriptor's layout and the arithmetic of a time step are described in include/viai_hip.h and DESIGN.md 11.2 / 11.2b.
@@ -21,18 +22,25 @@ import torch
 from . import _lib, wavenet as W
 from .ops import _ptr, _stream
 
-_Inputs = namedtuple("_Inputs", "B T tin tcls init_rows cond u1 u2 g_vec")
+_Inputs = namedtuple("_Inputs", "B T tin tcls init_rows cond u1 u2 g_vec forced")
 # per layer (lists): w_conv .. b_stage; w_c / b_c hold None without conditioning, w_stage / b_stage without the fused stages.  w_first_t: one-hot network only.
 _LAYER_FIELDS = ("w_conv", "b_conv", "w_c", "b_c", "w_out", "b_out", "w_skip", "b_skip", "w_stage", "b_stage")          # of `_lib.WnLayer`: a list each
 _NET_FIELDS = ("w_first", "b_first", "w_first_t", "w_l1", "b_l1", "w_l2", "b_l2")                                       # of `_lib.WnSynth`
 _Weights = namedtuple("_Weights", _LAYER_FIELDS + _NET_FIELDS)
 
 
-def _resolve_inputs(net, initial_input, c, g, T, test_inputs, softmax, quantize, uniforms, return_logits, return_classes, input_form):
-    """The checks of the arguments (the one-hot network's four come first: nothing has touched the library or the device by then) and the inputs
-    as the kernels read them: tin (B, n, K) / (B, n), tcls (B, n) int32 where the teacher-forced rows are exactly one-hot, init_rows (B, K),
-    cond (B, T, cin), the uniforms u1 (B, T, 10) / u2 (B, T), g_vec (B, gin, 1)."""
+def _resolve_inputs(net, initial_input, c, g, T, test_inputs, softmax, quantize, uniforms, return_logits, return_classes, input_form, forced=None,
+                    c_upsampled=False):
+    """The checks of the arguments (the one-hot network's four and the mask's come first: nothing has touched the library or the device by then)
+    and the inputs as the kernels read them: tin (B, n, K) / (B, n), tcls (B, n) int32 where the teacher-forced rows are exactly one-hot (or were
+    given as integer classes), init_rows (B, K), cond (B, T, cin), the uniforms u1 (B, T, 10) / u2 (B, T), g_vec (B, gin, 1), forced (B, T) uint8.
+    With `forced` the number of steps is the mask's and test_inputs must have exactly that length; rows the mask does not force are never read."""
     cat, K = not net.scalar_input, net.out_channels
+    if forced is not None:
+        if test_inputs is None:
+            raise ValueError("incremental_forward: forced= marks which steps of test_inputs are used; it needs test_inputs")
+        if forced.dim() != 2 or forced.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("incremental_forward: forced is a (B, T) bool or uint8 tensor")
     if cat:
         if quantize and not softmax:
             raise ValueError("incremental_forward: quantize=True needs softmax=True (logits are no probabilities to draw a class from)")
@@ -45,21 +53,37 @@ def _resolve_inputs(net, initial_input, c, g, T, test_inputs, softmax, quantize,
     dev = net.first_conv.bias.device
     tin = tcls = init_rows = None
     if test_inputs is not None:
-        if test_inputs.size(1) == (K if cat else 1):
+        as_classes = cat and test_inputs.dim() == 2 and not torch.is_floating_point(test_inputs)      # (B, n) integer classes: no one-hot tensor
+        if as_classes and input_form == "dense":
+            raise ValueError("incremental_forward: integer classes as test_inputs have no dense form")
+        if not as_classes and test_inputs.size(1) == (K if cat else 1):
             test_inputs = test_inputs.transpose(1, 2)                                 # -> (B, n, K) / (B, n, 1)  (wavenet.py:268-274)
         B = test_inputs.size(0)
+        if forced is not None:
+            if forced.size(0) != B:
+                raise ValueError("incremental_forward: forced is (B, T); it has %d rows, test_inputs %d streams" % (forced.size(0), B))
+            if test_inputs.size(1) != forced.size(1):
+                raise ValueError("incremental_forward: forced covers %d steps, test_inputs %d; a mask needs test_inputs of exactly its length"
+                                 % (forced.size(1), test_inputs.size(1)))
+            T = forced.size(1)
+            forced = forced.to(dev).to(torch.uint8).contiguous()
         T = test_inputs.size(1) if T is None else max(int(T), test_inputs.size(1))
-        if cat:
+        if as_classes:
+            tcls = test_inputs.to(dev).to(torch.int32).contiguous()
+        elif cat:
             tin = test_inputs.to(dev).float().contiguous()                            # (B, n, K)
             assert tin.size(2) == K, "test_inputs: (B, K, n) or (B, n, K)"
-            if input_form == "auto" and bool((((tin == 0) | (tin == 1)).all(-1) & (tin.sum(-1) == 1)).all()):
+            hot = ((tin == 0) | (tin == 1)).all(-1) & (tin.sum(-1) == 1)
+            if forced is not None:
+                hot = hot | (forced == 0)                                             # rows the mask does not force may hold anything
+            if input_form == "auto" and bool(hot.all()):
                 tcls = tin.argmax(-1).to(torch.int32).contiguous()                    # exactly one-hot rows: the class form
         else:
             tin = test_inputs.reshape(B, -1).to(dev).float().contiguous()
     else:
         B = c.size(0) if c is not None else (initial_input.size(0) if (cat and initial_input is not None) else 1)
     T = int(T)
-    if cat and initial_input is None and tin is None and K <= 127:
+    if cat and initial_input is None and tin is None and tcls is None and K <= 127:
         raise ValueError("incremental_forward: the default initial input is class 127 (wavenet.py:308-312); with %d classes pass initial_input" % K)
     if cat and initial_input is not None:                                             # wavenet.py:316-318
         if initial_input.size(1) == K:
@@ -69,7 +93,7 @@ def _resolve_inputs(net, initial_input, c, g, T, test_inputs, softmax, quantize,
         raise NotImplementedError("incremental_forward: 1 to 32 streams")
     cond = None
     if c is not None:
-        cu = net._upsample(c.to(dev).float())
+        cu = c.to(dev).float() if c_upsampled else net._upsample(c.to(dev).float())
         assert cu.size(-1) == T
         cond = cu.transpose(1, 2).contiguous()                                        # (B, T, cin)
     if cat:
@@ -84,7 +108,7 @@ def _resolve_inputs(net, initial_input, c, g, T, test_inputs, softmax, quantize,
     if g is not None:                                                                # wavenet.py:284-290: time-invariant
         g = g.to(dev)
         g_vec = (net.embed_speakers(g.view(B, -1)).transpose(1, 2) if net.embed_speakers is not None else g.float().view(B, -1, 1)).contiguous()
-    return _Inputs(B, T, tin, tcls, init_rows, cond, u1, u2, g_vec)
+    return _Inputs(B, T, tin, tcls, init_rows, cond, u1, u2, g_vec, forced)
 
 
 def _f32(x):
@@ -160,7 +184,7 @@ class _SynthState:
             L.ring, L.dilation, L.ring_len, L.g_add = self.rings[i].data_ptr(), d, 2 * d + 1, _ptr(self.g_add[i])
         st = self.desc = _lib.WnSynth()
         st.B, st.C, st.G, st.S, st.cin, st.n_layers, st.out_ch, st.T = B, Cc, G, S, (inp.cond.size(2) if inp.cond is not None else 4), len(self.dilations), K, T
-        st.n_test = inp.tin.size(1) if inp.tin is not None else 0
+        st.n_test = inp.tin.size(1) if inp.tin is not None else (inp.tcls.size(1) if inp.tcls is not None else 0)
         st.log_scale_min = float(log_scale_min)
         st.layers = self.layers
         for k in _NET_FIELDS:
@@ -181,12 +205,13 @@ class _SynthState:
         return (res, self.logits) if return_logits else res
 
 
-def _synth_form(use_graph, fuse, pipe_env, pipe_ok, categorical_ok, cat, B, T):
+def _synth_form(use_graph, fuse, pipe_env, pipe_ok, categorical_ok, cat, B, T, masked=False):
     """The launch form of a synthesis call.  "pipe": the pipelined form (csrc/wavenet_pipe.hip), one persistent launch, the stages work on
     different streams at the same time -- reference-size network with local conditioning only (pipe_ok: `viai_wn_pipe_ok`).  Everything else takes
     the chain of launches: "graph" (use_graph: one step with the time index on the device, captured once and replayed) or "chain" (the C side
-    loops over the time steps).  pipe_env: VIAI_WN_PIPE != 0; categorical_ok: `viai_wn_categorical_ok`, looked at for the one-hot network only."""
-    pipe = (not use_graph) and fuse and pipe_env and pipe_ok
+    loops over the time steps).  pipe_env: VIAI_WN_PIPE != 0; categorical_ok: `viai_wn_categorical_ok`, looked at for the one-hot network only.
+    masked: the call carries a mask of forced steps, which the chain forms take and the pipelined kernel does not."""
+    pipe = (not use_graph) and fuse and pipe_env and pipe_ok and not masked
     if not pipe and B not in (1, 2, 4, 8):
         raise NotImplementedError("incremental_forward: the chain of launches takes 1, 2, 4 or 8 streams; any other count up to 32 needs the pipelined form "
                                   "(reference-size network, local conditioning only, no use_graph, VIAI_WN_PIPE != 0, a device with 256 compute units)")
@@ -215,21 +240,29 @@ def _timed_chunks(timing, T, chunk, launch, tqdm):
 
 def _run_chain(lib, state, timing, tqdm):
     """default: the C side loops over the time steps and hands every kernel its time index by value"""
-    ref = Ct.byref(state.desc)
-    _timed_chunks(timing, state.inp.T, 64, lambda t0, n: _lib.check(lib.viai_wavenet_synth_run(ref, t0, n, _stream()), "viai_wavenet_synth_run"), tqdm)
+    ref, forced = Ct.byref(state.desc), state.inp.forced
+    if forced is None:
+        launch = lambda t0, n: _lib.check(lib.viai_wavenet_synth_run(ref, t0, n, _stream()), "viai_wavenet_synth_run")
+    else:
+        launch = lambda t0, n: _lib.check(lib.viai_wavenet_synth_run_forced(ref, forced.data_ptr(), t0, n, _stream()), "viai_wavenet_synth_run_forced")
+    _timed_chunks(timing, state.inp.T, 64, launch, tqdm)
 
 
 def _run_graph(lib, state, timing, tqdm):
     """device-side time index: one step captured into a HIP graph and replayed (every kernel starts with a load of the index)"""
-    ref = Ct.byref(state.desc)
+    ref, forced = Ct.byref(state.desc), state.inp.forced
+    if forced is None:
+        step = lambda: _lib.check(lib.viai_wavenet_synth_step(ref, _stream()), "viai_wavenet_synth_step")
+    else:
+        step = lambda: _lib.check(lib.viai_wavenet_synth_step_forced(ref, forced.data_ptr(), _stream()), "viai_wavenet_synth_step_forced")
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        _lib.check(lib.viai_wavenet_synth_step(ref, _stream()), "viai_wavenet_synth_step")          # step 0 (warm-up)
+        step()                                                                        # step 0 (warm-up)
     torch.cuda.current_stream().wait_stream(side)
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        _lib.check(lib.viai_wavenet_synth_step(ref, _stream()), "viai_wavenet_synth_step")          # captured: step 1
+        step()                                                                        # captured: step 1
     for _ in tqdm(range(state.inp.T - 1)):
         graph.replay()
 
@@ -259,9 +292,10 @@ _RUNNERS = {"pipe": _run_pipe, "graph": _run_graph, "chain": _run_chain}
 
 
 def incremental_forward(net, initial_input, c, g, T, test_inputs, tqdm, softmax, quantize, log_scale_min, uniforms, use_graph, return_logits,
-                        timing, return_classes, input_form):
+                        timing, return_classes, input_form, forced=None, c_upsampled=False):
     """`WaveNet.incremental_forward` (documented there)."""
-    inp = _resolve_inputs(net, initial_input, c, g, T, test_inputs, softmax, quantize, uniforms, return_logits, return_classes, input_form)
+    inp = _resolve_inputs(net, initial_input, c, g, T, test_inputs, softmax, quantize, uniforms, return_logits, return_classes, input_form, forced,
+                          c_upsampled)
     lib = _lib.load()
     f0 = net.conv_layers[0]
     fuse = (os.environ.get("VIAI_WN_FUSED", "1") != "0" and f0.conv1x1_skip.bias.numel() <= 256 and net.out_channels <= 256
@@ -269,7 +303,7 @@ def incremental_forward(net, initial_input, c, g, T, test_inputs, tqdm, softmax,
     state = _SynthState(net, inp, _synth_weights(net, inp.cond is not None, fuse), fuse, softmax, quantize, log_scale_min, return_logits, return_classes)
     ref = Ct.byref(state.desc)
     form = _synth_form(use_graph, fuse, os.environ.get("VIAI_WN_PIPE", "1") != "0", bool(lib.viai_wn_pipe_ok(ref)),
-                       bool(lib.viai_wn_categorical_ok(ref)), not net.scalar_input, inp.B, inp.T)
+                       bool(lib.viai_wn_categorical_ok(ref)), not net.scalar_input, inp.B, inp.T, inp.forced is not None)
     _RUNNERS[form](lib, state, timing, tqdm)
     torch.cuda.current_stream().synchronize()
     return state.result(return_logits, return_classes)
