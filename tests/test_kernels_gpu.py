@@ -402,6 +402,68 @@ def test_fused_layer_accuracy_against_fp64(shape):
         assert relerr(h, t) < 5 * relerr(c32, t) + 1e-6, (nm, relerr(h, t), relerr(c32, t))
 
 
+
+PLAN_CASES = [
+    # name, route, conv (transposed, Cin, Cout, k, s, p), input (N, H, W), tail, next_conv channels, out_p16 the plan gives with P16 on
+    ("plain", "plain", (False, 32, 32, 3, 1, 1), (2, 16, 16), None, 32, False),
+    ("tail-residual", "tail", (False, 32, 32, 3, 1, 1), (2, 16, 16), "residual", 32, False),
+    ("tail-pool", "tail", (False, 3, 64, 7, 2, 3), (2, 32, 32), "pool", 64, False),
+    ("up", "up", (True, 32, 32, 3, 1, 1), (2, 8, 6), (16, 12), 32, False),
+    ("instance", "instance", (False, 32, 32, 3, 1, 1), (2, 8, 8), None, 32, False),
+    # the same layers where the 3 x 3 conv behind them stages pre-split pieces (64 x 64 maps): planes, planes, and the twin of both tails
+    ("plain-p16", "plain", (False, 32, 32, 3, 1, 1), (2, 64, 64), None, 32, True),
+    ("tail-residual-twin", "tail", (False, 32, 32, 3, 1, 1), (2, 64, 64), "residual", 32, True),
+    ("tail-pool-twin", "tail", (False, 3, 64, 7, 2, 3), (2, 256, 256), "pool", 64, True),
+    ("up-p16", "up", (True, 32, 32, 3, 1, 1), (2, 32, 24), (64, 64), 32, True),
+]
+
+
+@pytest.mark.parametrize("case", PLAN_CASES, ids=[c[0] for c in PLAN_CASES])
+def test_fused_layer_runs_what_plan_layer_planned(case):
+    """networks.fused_layer is plan_layer, then one ops.conv_bn_act call and the passes behind it: for one layer per route the output is planes
+    / carries a twin exactly where the plan says so, and its (decoded) values are the fp64 torch composition's under the tolerance of
+    test_fused_layer_accuracy_against_fp64.  The residual comes from a 1 x 1 conv + BatchNorm layer (a BasicBlock's downsample branch), so
+    that it carries the magnitude a join needs to write its twin."""
+    from viai_amd import networks as N_, ops
+    name, route, (tr, Ci, Co, k, s_, p), (N, H, W), tail, Cn, want_p16 = case
+    conv = (torch.nn.ConvTranspose2d if tr else torch.nn.Conv2d)(Ci, Co, k, s_, p, bias=False)
+    norm = torch.nn.InstanceNorm2d(Co, affine=True) if route == "instance" else torch.nn.BatchNorm2d(Co)
+    down, down_bn = torch.nn.Conv2d(Ci, Co, 1, bias=False), torch.nn.BatchNorm2d(Co)
+    with torch.no_grad():
+        conv.weight.copy_(O.cf_std("pl.w", tuple(conv.weight.shape), 0.05)); down.weight.copy_(O.cf_std("pl.wd", tuple(down.weight.shape), 0.1))
+        norm.weight.copy_(O.cf_uniform("pl.g", (Co,), 0.8, 1.2)); norm.bias.copy_(O.cf_uniform("pl.b", (Co,), -0.1, 0.1))
+    x = O.cf_uniform("pl.x", (N, Ci, H, W), -1, 1)
+
+    def run(dt):
+        def bn_(t, m):
+            return F.batch_norm(t, None, None, m.weight.to(dt), m.bias.to(dt), True, 0.1, 1e-5)
+        y = (F.conv_transpose2d if tr else F.conv2d)(x.to(dt), conv.weight.detach().to(dt), None, stride=s_, padding=p)
+        y = F.instance_norm(y, None, None, norm.weight.to(dt), norm.bias.to(dt), True, 0.1, 1e-5) if route == "instance" else bn_(y, norm)
+        if tail == "residual":
+            y = y + bn_(F.conv2d(x.to(dt), down.weight.detach().to(dt)), down_bn)
+        y = F.relu(y)
+        if tail == "pool":
+            y = F.max_pool2d(y, 3, 2, 1)
+        return F.interpolate(y, size=list(tail), mode="bilinear", align_corners=True) if isinstance(tail, tuple) else y
+    with torch.no_grad():
+        truth, cpu32 = run(torch.float64), run(torch.float32)
+    conv, norm, down, down_bn = [m.cuda().train() for m in (conv, norm, down, down_bn)]
+    nxt = torch.nn.Conv2d(Cn, Cn, 3, 1, 1).cuda()
+    xg = ops.frames_to_nhwc4(x.cuda()) if tail == "pool" else nhwc(x)
+    kw = {"pool": (3, 2, 1)} if tail == "pool" else {"upsample": tail} if isinstance(tail, tuple) else {}
+    plan = N_.plan_layer(xg.shape, conv, norm, ops.ACT_RELU, has_residual=(tail == "residual"), next_conv=nxt, **kw)
+    assert (plan.route, plan.out_p16, plan.behind) == (route, want_p16 and ops.P16, ())
+    if tail == "residual":
+        kw["residual"] = N_.fused_layer(xg, down, down_bn, ops.ACT_NONE)
+    z = N_.fused_layer(xg, conv, norm, ops.ACT_RELU, next_conv=nxt, **kw)
+    assert ops.is_p16(z) == (plan.out_p16 and route != "tail")
+    assert (getattr(z, "_viai_twin", None) is not None) == (plan.out_p16 and route == "tail")
+    zs = [("z", ops.p16_decode(z))] + ([("twin", ops.p16_decode(z._viai_twin))] if hasattr(z, "_viai_twin") else [])
+    for nm, h in zs:
+        print(name, nm, "rel err %.3e, torch CPU fp32 %.3e" % (relerr(nchw(h), truth), relerr(cpu32, truth)))
+        assert relerr(nchw(h), truth) < 5 * relerr(cpu32, truth) + 1e-6, (nm, relerr(nchw(h), truth), relerr(cpu32, truth))
+
+
 def test_bn_large_mean_is_stable():
     """variance of a channel with mean >> std (the E[x^2]-E[x]^2 trap)."""
     from viai_amd import ops

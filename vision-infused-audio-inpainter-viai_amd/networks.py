@@ -16,6 +16,7 @@ data is NHWC.  Tensors returned to the caller are NCHW *views* of NHWC storage
 """
 from __future__ import annotations
 
+import collections
 import os
 
 import torch
@@ -80,16 +81,15 @@ class _InstanceNormHolder:
         self.bias = inorm.bias if inorm.affine else torch.zeros(c, device=device)
 
 
-def _instance_norm_layer(x, conv, inorm, act, x2, transposed):
+def _instance_norm_layer(layer, x, x2, inorm):
+    """layer(x, x2, norm holder) once per sample, with the keyword set of the caller's one ops.conv_bn_act call"""
     h = getattr(inorm, "_viai_holder", None)
     if h is None or h.weight.device != x.device:
         h = _InstanceNormHolder(inorm, x.device)
         object.__setattr__(inorm, "_viai_holder", h)
     if inorm.affine:
         h.weight, h.bias = inorm.weight, inorm.bias
-    outs = [ops.conv_bn_act(x[i:i + 1], conv.weight, conv.bias, h, kernel=_pair(conv.kernel_size), stride=_pair(conv.stride),
-                            padding=_pair(conv.padding), transposed=transposed, act=act,
-                            x2=(x2[i:i + 1] if x2 is not None else None), training=True) for i in range(x.shape[0])]
+    outs = [layer(x[i:i + 1], x2[i:i + 1] if x2 is not None else None, h) for i in range(x.shape[0])]
     return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
 
@@ -103,32 +103,92 @@ FUSE_BN_TAIL = True      # BatchNorm apply + (residual add + ReLU | ReLU + max-p
 # pre-split conv1 runs on the linear-tile loader / consumer kernel (csrc/conv_halo_dma.hip), 110.1 -> 108.1 ms on the vision-infused step -- ON.
 P16_TWIN = True
 
+ConvGeom = collections.namedtuple("ConvGeom", "kernel stride padding transposed ok")
+
+
+def _conv_geom(conv):
+    """the one reader of a conv holder: kernel, stride and padding as pairs, whether it is transposed, and `ok`: the HIP path takes the
+    holder as it stands (a 2-D conv, groups 1, dilation 1, transposed only at stride 1)"""
+    tr, stride = isinstance(conv, nn.ConvTranspose2d), _pair(conv.stride)
+    ok = isinstance(conv, (nn.Conv2d, nn.ConvTranspose2d)) and conv.groups == 1 and _pair(conv.dilation) == (1, 1) and not (tr and stride != (1, 1))
+    return ConvGeom(_pair(conv.kernel_size), stride, _pair(conv.padding), tr, ok)
+
 
 def takes_p16(x_shape, conv):
     """will `conv` (the layer behind a BatchNorm pass) stage a pre-split (P16) input of this NHWC shape?  (ops.conv_takes_p16)"""
-    tr = isinstance(conv, nn.ConvTranspose2d)
-    if not isinstance(conv, (nn.Conv2d, nn.ConvTranspose2d)) or getattr(conv, "groups", 1) != 1 or _pair(conv.dilation) != (1, 1):
-        return False
-    if tr and _pair(conv.stride) != (1, 1):
-        return False
-    return ops.conv_takes_p16(tuple(x_shape), conv.weight, _pair(conv.kernel_size), _pair(conv.stride), _pair(conv.padding), tr)
+    g = _conv_geom(conv)
+    return g.ok and ops.conv_takes_p16(tuple(x_shape), conv.weight, g.kernel, g.stride, g.padding, g.transposed)
 
 
 def wgrad_takes_p16(x_shape, conv):
     """... or at least in its weight-gradient kernel (ops.conv_wgrad_takes_p16: the stride-2 3 x 3 convs of the ResNet branch)?"""
-    tr = isinstance(conv, nn.ConvTranspose2d)
-    if not isinstance(conv, (nn.Conv2d, nn.ConvTranspose2d)) or getattr(conv, "groups", 1) != 1 or _pair(conv.dilation) != (1, 1) or tr:
-        return False
-    return ops.conv_wgrad_takes_p16(tuple(x_shape), conv.weight, _pair(conv.kernel_size), _pair(conv.stride), _pair(conv.padding), tr)
+    g = _conv_geom(conv)
+    return g.ok and not g.transposed and ops.conv_wgrad_takes_p16(tuple(x_shape), conv.weight, g.kernel, g.stride, g.padding, False)
 
 
 def out_shape(x_shape, conv):
     """NHWC shape of conv(x)"""
     N, H, W, _ = x_shape
-    k, s, p = _pair(conv.kernel_size), _pair(conv.stride), _pair(conv.padding)
-    if isinstance(conv, nn.ConvTranspose2d):
+    k, s, p, tr, _ = _conv_geom(conv)
+    if tr:
         return (N, (H - 1) * s[0] - 2 * p[0] + k[0], (W - 1) * s[1] - 2 * p[1] + k[1], conv.out_channels)
     return (N, (H + 2 * p[0] - k[0]) // s[0] + 1, (W + 2 * p[1] - k[1]) // s[1] + 1, conv.out_channels)
+
+
+def pooled_shape(shape, pool):
+    """NHWC shape of ops.maxpool(.., *pool), pool = (k, s, p)"""
+    k, s, p = pool
+    return (shape[0], (shape[1] + 2 * p - k) // s + 1, (shape[2] + 2 * p - k) // s + 1, shape[3])
+
+
+# What fused_layer decides about one conv -> norm -> act layer, before anything is launched:
+#   route     "instance": an nn.InstanceNorm2d holder.  One conv + BatchNorm(train) call per sample, so it always trains and is never P16; the
+#                         executor applies `xmask` with ops.mask_mul first; residual and pool run behind it.
+#             "tail":     the ops.conv_bn_act call takes residual / pool itself.  Needs FUSE_BN_TAIL, a _BatchNorm, act ReLU / none.
+#             "up":       the call takes the resize itself.  Needs ops.upsample_fusable and no residual, pool or xmask.
+#             "plain":    the call takes neither; whatever was asked for runs behind it.
+#   geom      _conv_geom(conv)
+#   act       handed to ops.conv_bn_act.  "instance" and "plain" run a layer with a residual WITHOUT activation: it follows the sum (`behind`).
+#   training  handed to ops.conv_bn_act: bn.training on "tail" and "up"; True on "instance"; on "plain" bn.training when there is a bn, else the argument.
+#   out_p16   handed to ops.conv_bn_act, and only ever True for a _BatchNorm in training mode whose `next_conv` takes the planes:
+#             "plain" -- z AS planes, only without residual and pool, takes_p16 at the conv's output shape;
+#             "up"    -- z as planes, takes_p16 at the RESIZED shape;
+#             "tail"  -- a TWIN beside the fp32 z (the join's output has other readers): P16_TWIN and (takes_p16 or wgrad_takes_p16), at the
+#                        pooled shape when there is a pool.
+#   behind    the passes of their own that follow the call, in order, out of "add_relu" | "add" (the residual, act ReLU | none), "maxpool",
+#             "bilinear_ac".  A resize that is not fused runs here, and its layer is planned WITHOUT `next_conv` (the resize reads fp32), so
+#             that layer's output is never P16.
+LayerPlan = collections.namedtuple("LayerPlan", "route geom act training out_p16 behind")
+_Shaped = collections.namedtuple("_Shaped", "shape")          # what ops.upsample_fusable reads of x
+
+
+def plan_layer(x_shape, conv, bn, act, *, has_xmask=False, has_residual=False, pool=None, upsample=None, next_conv=None, training=True):
+    """the LayerPlan of fused_layer(x, conv, bn, act, ...) for an x of this NHWC shape.  Launches and allocates nothing: it reads shapes, holder
+    types and flags, the switches (FUSE_BN_TAIL, P16_TWIN, ops.P16, ops.F16_BACKWARD, ops.FUSE_BN_UP) and the library's answers
+    (ops.conv_takes_p16, ops.conv_wgrad_takes_p16, ops.upsample_fusable), and asks those no more often than it must: `next_conv`, the
+    switches and bn.training come first."""
+    g = _conv_geom(conv)
+    if g.transposed and g.stride != (1, 1):
+        raise NotImplementedError("ConvTranspose2d stride != 1")
+    if has_residual and act not in (ACT_RELU, ACT_NONE):
+        raise ValueError("fused_layer: a residual takes ReLU or no activation")
+    batchnorm = isinstance(bn, nn.modules.batchnorm._BatchNorm)
+    join = (("add_relu" if act == ACT_RELU else "add",) if has_residual else ()) + (("maxpool",) if pool is not None else ())
+    resize = ()
+    if upsample is not None:
+        up = (int(upsample[0]), int(upsample[1]))
+        if not join and not has_xmask and ops.upsample_fusable(_Shaped(x_shape), conv.weight, conv.bias, bn, g.transposed, act, up):
+            p16 = next_conv is not None and bn.training and takes_p16((x_shape[0], up[0], up[1], conv.out_channels), next_conv)
+            return LayerPlan("up", g, act, bn.training, p16, ())
+        resize, next_conv = ("bilinear_ac",), None
+    if isinstance(bn, nn.InstanceNorm2d):
+        return LayerPlan("instance", g, ACT_NONE if has_residual else act, True, False, join + resize)
+    if FUSE_BN_TAIL and batchnorm and act in (ACT_RELU, ACT_NONE) and join:
+        oshape = out_shape(x_shape, conv) if pool is None else pooled_shape(out_shape(x_shape, conv), pool)
+        twin = P16_TWIN and next_conv is not None and bn.training and (takes_p16(oshape, next_conv) or wgrad_takes_p16(oshape, next_conv))
+        return LayerPlan("tail", g, act, bn.training, twin, resize)
+    p16 = next_conv is not None and not join and batchnorm and bn.training and takes_p16(out_shape(x_shape, conv), next_conv)
+    return LayerPlan("plain", g, ACT_NONE if has_residual else act, bn.training if bn is not None else training, p16, join + resize)
 
 
 def fused_layer(x, conv, bn, act, x2=None, training=True, xmask=None, residual=None, pool=None, upsample=None, next_conv=None):
@@ -138,57 +198,37 @@ def fused_layer(x, conv, bn, act, x2=None, training=True, xmask=None, residual=N
     a hook that reads values -- drops the tag and reinterprets the planes as fp32.  ops.p16_decode gives the values.
     conv (nn.Conv2d | nn.ConvTranspose2d holder) -> bn (nn.BatchNorm2d | nn.InstanceNorm2d holder | None) -> act, on NHWC.
     `xmask`: the layer convolves x * xmask (ops.conv_bn_act).  `upsample` = (H, W): F.interpolate(.., align_corners=True) behind the
-    layer -- inside the BatchNorm apply pass where ops.upsample_fusable allows, as a pass of its own otherwise."""
-    transposed = isinstance(conv, nn.ConvTranspose2d)
-    if transposed and _pair(conv.stride) != (1, 1):
-        raise NotImplementedError("ConvTranspose2d stride != 1")
-    if upsample is not None:
-        up = (int(upsample[0]), int(upsample[1]))
-        if residual is None and pool is None and xmask is None and ops.upsample_fusable(x, conv.weight, conv.bias, bn, transposed, act, up):
-            p16 = (next_conv is not None and isinstance(bn, nn.modules.batchnorm._BatchNorm) and bn.training
-                   and takes_p16((x.shape[0], up[0], up[1], conv.out_channels), next_conv))
-            return ops.conv_bn_act(x, conv.weight, conv.bias, bn, kernel=_pair(conv.kernel_size), stride=_pair(conv.stride),
-                                   padding=_pair(conv.padding), transposed=transposed, act=act, x2=x2, training=bn.training, upsample=up, out_p16=p16)
-        return ops.bilinear_ac(fused_layer(x, conv, bn, act, x2=x2, training=training, xmask=xmask, residual=residual, pool=pool), up)
-    if isinstance(bn, nn.InstanceNorm2d):
-        if xmask is not None:
-            x = ops.mask_mul(x, xmask)
-        out = _instance_norm_layer(x, conv, bn, ACT_NONE if residual is not None else act, x2, transposed)
-        if residual is not None:
-            out = ops.add_relu(out, residual) if act == ACT_RELU else out + residual
-        return ops.maxpool(out, *pool) if pool is not None else out
-    if FUSE_BN_TAIL and isinstance(bn, nn.modules.batchnorm._BatchNorm) and act in (ACT_RELU, ACT_NONE) and (residual is not None or pool is not None):
-        # a residual join whose output feeds `next_conv` AND other readers (the next join, a downsample conv) writes a pre-split twin beside the fp32 tensor
-        oshape = out_shape(x.shape, conv)
-        if pool is not None:
-            oshape = (oshape[0], (oshape[1] + 2 * pool[2] - pool[0]) // pool[1] + 1, (oshape[2] + 2 * pool[2] - pool[0]) // pool[1] + 1, oshape[3])
-        twin = P16_TWIN and next_conv is not None and bn.training and (takes_p16(oshape, next_conv) or wgrad_takes_p16(oshape, next_conv))
-        return ops.conv_bn_act(x, conv.weight, conv.bias, bn, kernel=_pair(conv.kernel_size), stride=_pair(conv.stride),
-                               padding=_pair(conv.padding), transposed=transposed, act=act, x2=x2, training=bn.training, xmask=xmask,
-                               residual=residual, pool=pool, out_p16=twin)
-    p16 = (next_conv is not None and residual is None and pool is None and isinstance(bn, nn.modules.batchnorm._BatchNorm) and bn.training
-           and takes_p16(out_shape(x.shape, conv), next_conv))
-    out = ops.conv_bn_act(x, conv.weight, conv.bias, bn, kernel=_pair(conv.kernel_size), stride=_pair(conv.stride),
-                          padding=_pair(conv.padding), transposed=transposed, act=(ACT_NONE if residual is not None else act), x2=x2,
-                          training=(bn.training if bn is not None else training), xmask=xmask, out_p16=p16)
-    if residual is not None:
-        out = ops.add_relu(out, residual) if act == ACT_RELU else out + residual
-    return ops.maxpool(out, *pool) if pool is not None else out
+    layer -- inside the BatchNorm apply pass where ops.upsample_fusable allows, as a pass of its own otherwise.
+    Plan, then run: every decision is plan_layer's (see LayerPlan)."""
+    plan = plan_layer(x.shape, conv, bn, act, has_xmask=xmask is not None, has_residual=residual is not None, pool=pool, upsample=upsample,
+                      next_conv=next_conv, training=training)
+    g, b = plan.geom, plan.behind
+    up = (int(upsample[0]), int(upsample[1])) if upsample is not None else None
+    inside = {"residual": residual, "pool": pool} if plan.route == "tail" else {"upsample": up} if plan.route == "up" else {}
+    xmask_in = None if plan.route == "instance" else xmask            # ("instance": multiplied in front, below)
+
+    def layer(xs, x2s, norm):
+        return ops.conv_bn_act(xs, conv.weight, conv.bias, norm, kernel=g.kernel, stride=g.stride, padding=g.padding, transposed=g.transposed,
+                               act=plan.act, x2=x2s, training=plan.training, xmask=xmask_in, out_p16=plan.out_p16, **inside)
+    if plan.route == "instance":
+        out = _instance_norm_layer(layer, x if xmask is None else ops.mask_mul(x, xmask), x2, bn)
+    else:
+        out = layer(x, x2, bn)
+    out = ops.add_relu(out, residual) if "add_relu" in b else out + residual if "add" in b else out
+    out = ops.maxpool(out, *pool) if "maxpool" in b else out
+    return ops.bilinear_ac(out, up) if "bilinear_ac" in b else out
 
 
 def fused_pair(x, conv, bn, act, conv2, act2, x2=None):
     """conv -> bn -> act -> conv2 (one output channel) -> act2.  Where the pair kernels apply (BatchNorm, conv2 3 x 3 / stride 1 / pad 1,
     width a multiple of 16: G.conv6_1 -> conv6_2 and D.conv3 -> conv4 at every shape the step runs) neither the tensor between the two
     layers nor conv2's data gradient is ever stored (ops.conv_bn_act_cout1); otherwise two fused layers."""
-    tr, tr2 = isinstance(conv, nn.ConvTranspose2d), isinstance(conv2, nn.ConvTranspose2d)
-    if (isinstance(bn, nn.modules.batchnorm._BatchNorm) and conv2.out_channels == 1 and (not tr or _pair(conv.stride) == (1, 1))
-            and _pair(conv2.dilation) == (1, 1) and _pair(conv.dilation) == (1, 1) and getattr(conv2, "groups", 1) == 1
-            and ops.conv_bn_act_cout1_ok(x, conv.weight, bn, conv2.weight, kernel=_pair(conv.kernel_size), stride=_pair(conv.stride),
-                                         padding=_pair(conv.padding), transposed=tr, kernel2=_pair(conv2.kernel_size),
-                                         stride2=_pair(conv2.stride), padding2=_pair(conv2.padding), x2=x2)):
-        return ops.conv_bn_act_cout1(x, conv.weight, conv.bias, bn, conv2.weight, conv2.bias, kernel=_pair(conv.kernel_size),
-                                     stride=_pair(conv.stride), padding=_pair(conv.padding), transposed=tr, act=act, transposed2=tr2,
-                                     act2=act2, x2=x2, training=bn.training)
+    g, g2 = _conv_geom(conv), _conv_geom(conv2)
+    first = {"kernel": g.kernel, "stride": g.stride, "padding": g.padding, "transposed": g.transposed, "x2": x2}
+    if (isinstance(bn, nn.modules.batchnorm._BatchNorm) and conv2.out_channels == 1 and g.ok and g2.ok
+            and ops.conv_bn_act_cout1_ok(x, conv.weight, bn, conv2.weight, kernel2=g2.kernel, stride2=g2.stride, padding2=g2.padding, **first)):
+        return ops.conv_bn_act_cout1(x, conv.weight, conv.bias, bn, conv2.weight, conv2.bias, act=act, transposed2=g2.transposed, act2=act2,
+                                     training=bn.training, **first)
     return fused_layer(fused_layer(x, conv, bn, act, x2=x2), conv2, None, act2)
 
 
