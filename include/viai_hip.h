@@ -441,6 +441,25 @@ int viai_wn_window_gather(const float* wav, const int* classes, const float* con
  * fade == 0 is an exact copy on both sides.  g0, len: B int32 in device memory; out must not alias wav.                                         */
 int viai_wn_splice(const float* wav, const float* gen, const int* g0, const int* len, float* out, int B, int n, int L, int R, int fade, void* stream);
 
+/* ---- the join between the mel generator and the vocoder (csrc/inpaint_join.hip; additive to ABI v20) ----
+ * The mel front end follows lws (utils/audio.py:90-108): frames = n / hop + 3 for n % hop == 0, frame j reads the clip's samples
+ * [j hop - (fft - hop), j hop + hop).  The vocoder wants n == frames hop, so the clip moves right by lpad = fft - hop silent samples
+ * (utils/librivox.py:92-102: lws_pad_lr, then the cut to N hop).  On that ALIGNED grid, a = i + lpad, frame j owns the samples
+ * [j hop, (j + 1) hop) and its analysis window is [j hop, j hop + fft).  a0, a1 below are B int32 in device memory: one gap [a0[b], a1[b]) per
+ * stream in aligned coordinates, a0[b] >= a1[b] meaning no gap.  Each call is one launch; none does arithmetic on a sample or mel value, so the
+ * words that are copied keep their bits (NaN payloads included).  Output pointers need 4-byte alignment only.
+ *
+ * mask (B, frames) -- the memory of a (B, 1, 1, frames) time mask (1 = known, 0 = gap): a frame is damaged when its WINDOW meets the gap,
+ *     mask[b][j] = (a0[b] < a1[b] && j hop < a1[b] && j hop + fft > a0[b]) ? 0 : 1
+ * which is wider than the gap's own frames by the window's overhang (three frames on the left at 1024 / 256).  Any fft, hop >= 1.          */
+int viai_gap_frame_mask(const int* a0, const int* a1, float* mask, int B, int frames, int fft, int hop, void* stream);
+/* out (B, n + lpad): out[b][a] = 0 for a < lpad and for a0[b] <= a < a1[b], wav[b][a - lpad] otherwise.  wav (B, n); out must not alias wav. */
+int viai_wav_align(const float* wav, const int* a0, const int* a1, float* out, int B, int n, int lpad, void* stream);
+/* The vocoder's conditioning: real mel where the frame is clean, the generator's where it is damaged -- a select, not a blend:
+ *     c[b][f][t] = mask[b][t] != 0 ? real[b][f][t] : fake[b][f][t]
+ * real, fake (B, 1, F, T) contiguous, mask (B, T), c (B, F, T) (the layout wavenet.py:291-299 up-samples).  Any F, T >= 1.                     */
+int viai_mel_compose(const float* real, const float* fake, const float* mask, float* c, int B, int F, int T, void* stream);
+
 /* Incremental synthesis as ONE persistent launch (ABI v16, csrc/wavenet_pipe.hip): a weight-stationary pipeline for the reference-size
  * network (24 layers, 512 residual / 512 gate / 256 skip channels, 80 conditioning channels, 30 outputs, no global conditioning).  Every
  * stage owns compute units (10 per layer, 4 + 4 + 1 for the head) and keeps its weights in registers / LDS; the streams travel round the

@@ -9,5 +9,14 @@ name; the top-level `viai_amd/` shim maps the import name onto it).
   model     AudioModel: the G+D train step (reference: the missing Models/Whole_Sync_inpainting_modify)
   ddp       one-process-per-GPU gradient all-reduce over RCCL
   synth     closed-form synthetic MUSICES-shaped inputs
+  inpaint   AudioInpainter: waveform in, waveform out (mel front end -> generator -> WaveNet vocoder); gap_frames
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # `viai_amd.AudioInpainter` / `viai_amd.gap_frames`, resolved on first use: importing the package stays free of torch and the library
+    if name in ("AudioInpainter", "gap_frames"):
+        from . import inpaint
+        return getattr(inpaint, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

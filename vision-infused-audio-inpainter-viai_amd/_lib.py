@@ -160,6 +160,9 @@ SIGNATURES = {
     "viai_wavenet_synth_run_forced": (_I, [C.POINTER(WnSynth), _P, _I, _I, _P]),
     "viai_wn_window_gather": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "viai_wn_splice": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "viai_gap_frame_mask": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "viai_wav_align": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "viai_mel_compose": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "viai_wn_categorical_ok": (_I, [C.POINTER(WnSynth)]),
     "viai_mulaw_decode": (_I, [_P, _P, _L, _I, _P]),
     "viai_mulaw_quantize": (_I, [_P, _P, _L, _I, _P]),

@@ -425,10 +425,10 @@ def mulaw_quantize(x, mu=255):
     return out.long()
 
 
-def inpaint_waveform(net, wav, c, gap_start, gap_len, uniforms=None, fade=0, return_window=False):
+def inpaint_waveform(net, wav, c, gap_start, gap_len, uniforms=None, fade=0, return_window=False, gap_unit="frames"):
     """Fill one gap per stream of a waveform with the vocoder `net`: the receptive field in front of every gap is teacher-forced, the gap runs
-    free, everything else is copied (viai_amd/wavenet_inpaint.py, documented there)."""
-    return wavenet_inpaint.inpaint_waveform(net, wav, c, gap_start, gap_len, uniforms, fade, return_window)
+    free, everything else is copied (viai_amd/wavenet_inpaint.py, documented there).  gap_start / gap_len are frames, or samples with gap_unit="samples"."""
+    return wavenet_inpaint.inpaint_waveform(net, wav, c, gap_start, gap_len, uniforms, fade, return_window, gap_unit)
 
 
 def gaps_from_mask(mask):

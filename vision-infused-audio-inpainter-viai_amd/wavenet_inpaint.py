@@ -2,7 +2,7 @@
 spectrogram, and `WaveNet.incremental_forward`, which turns a mel into samples.
 
 Only the receptive field R in front of a gap and the gap itself need the sample-by-sample loop.  Per stream b, in samples (hop = the product of
-the up-sampling scales, g0 = gap_start * hop, len = gap_len * hop):
+the up-sampling scales, g0 = gap_start * hop, len = gap_len * hop; with gap_unit="samples" g0 = gap_start, len = gap_len):
 
     window      clip times [w_b, w_b + L),  w_b = g0_b - R,  L = R + max_b len_b          (viai_wn_window_gather)
     forced      window position t is teacher-forced unless R <= t < R + len_b              (the R known samples fill the ring buffers)
@@ -100,9 +100,10 @@ def _per_stream(x, B, name):
     return x
 
 
-def inpaint_waveform(net, wav, c, gap_start, gap_len, uniforms=None, fade=0, return_window=False):
+def inpaint_waveform(net, wav, c, gap_start, gap_len, uniforms=None, fade=0, return_window=False, gap_unit="frames"):
     """wav (B, n) floats in [-1, 1]; c (B, cin, frames) with n == frames * hop; gap_start / gap_len: frames, per stream ((B,) ints or a tensor, or
     one int for all).  Returns the (B, n) waveform with [gap_start, gap_start + gap_len) regenerated and every other sample copied bit for bit.
+    `gap_unit="samples"`: gap_start / gap_len are samples of `wav` (damage does not come in whole frames); the gap must lie inside the n samples.
 
     One-hot network: the window goes in as mu-law classes (`mulaw_quantize`, mu = out_channels - 1), the call samples (quantize=True) and the classes
     come out through `mulaw_decode`.  Scalar network: raw samples and the mixture-of-logistics sampler.
@@ -111,6 +112,8 @@ def inpaint_waveform(net, wav, c, gap_start, gap_len, uniforms=None, fade=0, ret
     `fade` > 0 blends the last `fade` samples of each gap linearly from generated to original (viai_wn_splice).
     `return_window=True`: also a dict with the windows' own samples (B, L), their starts (B,) in samples, and the mask of forced steps.
     Stream counts are those of `incremental_forward`'s chain forms (1, 2, 4 or 8)."""
+    if gap_unit not in ("frames", "samples"):
+        raise ValueError("inpaint_waveform: gap_unit is \"frames\" or \"samples\", not %r" % (gap_unit,))
     if wav.dim() != 2:
         raise ValueError("inpaint_waveform: wav is (B, n)")
     B, n = wav.shape
@@ -123,13 +126,14 @@ def inpaint_waveform(net, wav, c, gap_start, gap_len, uniforms=None, fade=0, ret
     if c.size(1) % 4 != 0:
         raise ValueError("inpaint_waveform: the conditioning channel count must be a multiple of 4")
     gs, gl = _per_stream(gap_start, B, "gap_start"), _per_stream(gap_len, B, "gap_len")
-    if bool((gs < 0).any()) or bool((gl < 0).any()) or bool((gs + gl > frames).any()):
-        raise ValueError("inpaint_waveform: a gap must lie inside the clip's %d frames" % frames)
+    unit, extent = (hop, frames) if gap_unit == "frames" else (1, n)
+    if bool((gs < 0).any()) or bool((gl < 0).any()) or bool((gs + gl > extent).any()):
+        raise ValueError("inpaint_waveform: a gap must lie inside the clip's %d %s" % (extent, gap_unit))
     if fade < 0:
         raise ValueError("inpaint_waveform: fade >= 0")
     dev = net.first_conv.bias.device
     R = int(net.receptive_field)
-    g0, ln = gs * hop, gl * hop
+    g0, ln = gs * unit, gl * unit
     L = R + int(ln.max())
     w = g0 - R
     wav_d = wav.to(dev).float().contiguous()
