@@ -527,6 +527,16 @@ int viai_stft_mel(const float* wav, const float* window, const float* basis_t, c
 int viai_stft_mel_banded(const float* wav, const float* window, const float* basis_t, const int* band_lo, const int* band_cnt,
                          const float* mask, float* mel, int B, int n_samples, int fft, int hop, int n_mels, int frames,
                          float min_level_db, float ref_level_db, void* stream);
+/* Which kernel family a front-end call of this shape runs on, without a launch (host code only; measurement aid, no reference
+ * counterpart).  fft = 1024 answers for viai_stft_mel_banded, which chooses by shape: "r512" (one real frame per wave as a 512-point
+ * complex FFT: n_mels <= 256, a hop that is a multiple of 8, an even n_samples and a `wav` pointer aligned to 8 bytes -- wav_aligned8 != 0),
+ * else "wave" (two real frames per wave as one 1024-point FFT: n_mels <= 1024, a hop that is a multiple of 8), else "banded" (the frame-batched
+ * kernel: any hop, any band count; the two wave kernels were measured wrong in the frames that cross a clip's start at hops 254, 255, 257).  fft = 512 / 2048 answer
+ * "dense": only viai_stft_mel serves them, on its one kernel (one frame per block, every bin of every band), which it also runs for
+ * fft = 1024.  The launch decides by the same function.  Whether the band weights are held in LDS depends on the sum of band_cnt,
+ * which is device data (r512: <= 1024, wave: <= 2048; else they are read from global memory): not part of the answer.
+ * family receives the NUL-terminated name (truncated to cap); returns 1, or 0 with an empty name where the entry point refuses.    */
+int viai_stft_mel_route(int n_samples, int fft, int hop, int n_mels, int wav_aligned8, char* family, int cap);
 
 /* -------------------------------------------------- callers either side of the path
  * Batch assembly on the device, Data_loaders/audio_loader.py:185-245: frames uint8 [n][S][S][C] (RGB or

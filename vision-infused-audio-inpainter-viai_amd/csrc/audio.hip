@@ -14,6 +14,7 @@
 #include "viai_common.h"
 #include "viai_internal.h"
 #include <cstdlib>
+#include <cstring>
 
 namespace {
 
@@ -679,25 +680,58 @@ int launch_stft_wave(int per_cu, const float* wav, const float* window, const fl
     return viai_launch_status();
 }
 
+// Kernel choice by shape, the ONE decision viai_stft_mel_banded launches by and viai_stft_mel_route reports (the A/B variants of round 4 -- two 4-wave blocks
+// per CU: 551 us on 1024 clips, the r512 kernel as two 8-wave blocks: 479 - 491 -- were measured, lost and are gone): a frame per wave as a 512-point FFT
+// (455 - 480 us) where the shape allows -- 8-byte sample pairs: an even clip length, an 8-byte aligned first clip --, else one 8-wave block per CU
+// (523), else the frame-batched kernel.  fft = 512 / 2048 are served by viai_stft_mel's one-frame-per-block kernel only.
+// Both wave kernels take hops that are multiples of 8 only.  Their zero padding left of a clip is a buffer load whose byte offset -- a negative register plus the
+// instruction's immediate -- must wrap to a huge unsigned one to read as zero, and that held only where the sign change inside a 64-lane load falls on a 16-byte
+// boundary, i.e. where every frame starts on a multiple of 4 samples: measured on the wave kernel (tests/test_stft_mel_routes_gpu.py), hops 192, 200, 256 and
+// 1024 agree with the fp64 oracle to 1.5e-6 of a frame's largest magnitude, hops 254, 255 and 257 are off by up to 9e-2 of it in the frames that cross the clip's
+// start (samples next to the start lost; no other frame, no stray read).  Other hops run on the frame-batched kernel (guarded plain loads): 4.4e-6 at hop 255.
+enum class StftRoute { refused, r512, wave, banded, dense };
+StftRoute stft_route(int n_samples, int fft, int hop, int n_mels, bool wav_aligned8) {
+    if (hop <= 0 || hop > fft || n_mels <= 0) return StftRoute::refused;
+    if (fft == 512 || fft == 2048) return StftRoute::dense;
+    if (fft != SB_N) return StftRoute::refused;
+    if (n_mels <= R5_MMAX && hop % 8 == 0 && n_samples % 2 == 0 && wav_aligned8) return StftRoute::r512;
+    if (n_mels <= 1024 && hop % 8 == 0) return StftRoute::wave;
+    return StftRoute::banded;
+}
+
 }  // namespace
+
+extern "C" int viai_stft_mel_route(int n_samples, int fft, int hop, int n_mels, int wav_aligned8, char* family, int cap) {
+    static const char* const names[] = {"", "r512", "wave", "banded", "dense"};
+    const StftRoute r = stft_route(n_samples, fft, hop, n_mels, wav_aligned8 != 0);
+    if (family != nullptr && cap > 0) {
+        strncpy(family, names[(int)r], (size_t)cap - 1);
+        family[cap - 1] = 0;
+    }
+    return r == StftRoute::refused ? 0 : 1;
+}
 
 // as viai_stft_mel for fft = 1024 with the support of every mel band given: band m is nonzero on bins [band_lo[m], band_lo[m] + band_cnt[m])
 extern "C" int viai_stft_mel_banded(const float* wav, const float* window, const float* basis_t, const int* band_lo, const int* band_cnt,
                                     const float* mask, float* mel, int B, int n_samples, int fft, int hop, int n_mels, int frames,
                                     float min_level_db, float ref_level_db, void* stream) {
     if (B <= 0 || frames <= 0 || hop <= 0 || hop > fft || n_mels <= 0 || fft != SB_N || band_lo == nullptr || band_cnt == nullptr) return (int)hipErrorInvalidValue;
-    // kernel choice by shape (the A/B variants of round 4 -- two 4-wave blocks per CU: 551 us on 1024 clips, the r512 kernel as two 8-wave blocks: 479 - 491 -- were
-    // measured, lost and are gone): a frame per wave as a 512-point FFT (455 - 480 us) where the shape allows, else one 8-wave block per CU (523), else the
-    // frame-batched kernel
-    if (n_mels <= R5_MMAX && hop % 2 == 0 && n_samples % 2 == 0 && (reinterpret_cast<uintptr_t>(wav) & 7) == 0)
-        return launch_stft_r512<16, 32, 20, 10>(1, wav, window, basis_t, band_lo, band_cnt, mask, mel, B, n_samples, hop, n_mels, frames, min_level_db, ref_level_db, (hipStream_t)stream);
-    if (n_mels <= 1024)
-        return launch_stft_wave<8, 32, 20, 2048, 1024>(1, wav, window, basis_t, band_lo, band_cnt, mask, mel, B, n_samples, hop, n_mels, frames, min_level_db, ref_level_db, (hipStream_t)stream);
+    const auto st = (hipStream_t)stream;
+    switch (stft_route(n_samples, fft, hop, n_mels, (reinterpret_cast<uintptr_t>(wav) & 7) == 0)) {
+    case StftRoute::r512:
+        return launch_stft_r512<16, 32, 20, 10>(1, wav, window, basis_t, band_lo, band_cnt, mask, mel, B, n_samples, hop, n_mels, frames, min_level_db, ref_level_db, st);
+    case StftRoute::wave:
+        return launch_stft_wave<8, 32, 20, 2048, 1024>(1, wav, window, basis_t, band_lo, band_cnt, mask, mel, B, n_samples, hop, n_mels, frames, min_level_db, ref_level_db, st);
+    case StftRoute::banded:
+        break;
+    default:
+        return (int)hipErrorInvalidValue;
+    }
     constexpr int lds = (8 * SB_N + 768) * (int)sizeof(float2);
     static bool attr_done = false;
     if (!attr_done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stft_mel_banded_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr_done = true; }
     dim3 grid((frames + SB_F - 1) / SB_F, B);
-    VIAI_LAUNCH(stft_mel_banded_kernel, grid, dim3(256), lds, (hipStream_t)stream, wav, window, basis_t, band_lo, band_cnt, mask, mel, n_samples, hop, n_mels,
+    VIAI_LAUNCH(stft_mel_banded_kernel, grid, dim3(256), lds, st, wav, window, basis_t, band_lo, band_cnt, mask, mel, n_samples, hop, n_mels,
                 frames, min_level_db, ref_level_db);
     return viai_launch_status();
 }
