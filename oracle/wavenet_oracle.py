@@ -209,19 +209,49 @@ def incremental_forward(sd, c, T, u1, u2, cfg=WNConfig, test_inputs=None, log_sc
     return out
 
 
-def incremental_forward_ring(sd, c, T, u1, u2, cfg=WNConfig, test_inputs=None, log_scale_min=-7.0, g=None, return_logits=False):
+def categorical_draw(p, u):
+    """np.random.choice(K, p=p) (wavenet.py:352-353) with the uniform draw injected: the inverse cdf, class = #{k: cdf[k] <= u} with
+    cdf = cumsum(p) / sum(p) in fp64 (numpy accumulates in double; searchsorted side="right"), at most K - 1.  p (B, K), u (B,) -> (B,) int64.
+    tests/golden/wavenet_onehot_synth.npz pins the rule (tests/test_wavenet_onehot_synth_cpu.py)."""
+    cdf = torch.cumsum(p.double(), dim=1)
+    cdf = cdf / cdf[:, -1:]
+    return (cdf <= u.double().reshape(-1, 1)).sum(1).clamp(max=p.shape[1] - 1)
+
+
+def incremental_forward_ring(sd, c, T, u1, u2, cfg=WNConfig, test_inputs=None, log_scale_min=-7.0, g=None, return_logits=False, dtype=None,
+                             softmax=True, quantize=True, initial_input=None, return_classes=False, forced=None, tap_hook=None):
     """WaveNet.incremental_forward (wavenet.py:237-364) the way the reference computes it: sample by sample, every dilated conv as a
     LINEAR layer over a ring buffer of its last (k - 1) d + 1 inputs (conv.py:17-46: shift the buffer, append the new input, gather
     every d-th entry, one matrix product with the (Cout, k Cin) linearised weight conv.py:53-57) -- O(T) work, unlike
     `incremental_forward` above (the definition-of-causality form used to pin it).  This is the CPU restatement bench.py times as the
-    `cpu_baseline` of configs[4]."""
+    `cpu_baseline` of configs[4].
+
+    dtype: None keeps every tensor as it comes (fp32 state: the behaviour bench.py times).  torch.float64 casts weight_v, weight_g, biases,
+    the embedding, conditioning, inputs and uniforms to double BEFORE the weight normalisation and allocates all state (rings, out, logits,
+    cur) in double: the fp64 truth of the same fp32 weights and inputs.
+    `c` with as many frames as time steps is already at the sample rate and skips the up-sampling stack (wavenet.py:303-304).
+    One-hot network (cfg.scalar_input False; wavenet.py:308-318, 345-361): test_inputs (B, K, n) rows or (B, n) integer classes, initial_input
+    (B, K) (default: class 127, or 0 where K <= 127, as the library's descriptor has it); the result is (B, K, T) -- softmax / quantize True / True the
+    one-hot rows of the classes drawn by `categorical_draw` from u2 (B, T) (u1 unused; return_classes: the (B, T) classes), True / False the
+    probabilities, False / False the logits, each fed back as it is.  return_logits adds the logits (B, K, T) in every mode.
+    forced: optional (B, T) bool mask -- the input of step t of stream b is test_inputs[b, t] where forced[b, t], else the previous output.
+    tap_hook: tests only -- a callable (t, layer, x (B, k, C)) -> x applied to the gathered taps (a deliberate defect)."""
+    scalar = getattr(cfg, "scalar_input", True)
+    K = cfg.out_channels
+    if dtype is not None:
+        cast = lambda v: v.to(dtype) if (torch.is_tensor(v) and torch.is_floating_point(v)) else v
+        sd = OrderedDict((n, cast(v)) for n, v in sd.items())
+        c, u1, u2, test_inputs, initial_input = cast(c), cast(u1), cast(u2), cast(test_inputs), cast(initial_input)
+    dt = sd["first_conv.bias"].dtype
     B = c.shape[0] if c is not None else (test_inputs.shape[0] if test_inputs is not None else 1)
     k = cfg.kernel_size
     per = cfg.layers // cfg.stacks
     sq = math.sqrt(0.5)
     with torch.no_grad():
         cu = None
-        if c is not None:                                                    # wavenet.py:291-299: up-sample once
+        if c is not None and c.shape[-1] == T:                               # wavenet.py:303-304: already at the sample rate
+            cu = c.transpose(1, 2).contiguous()
+        elif c is not None:                                                  # wavenet.py:291-299: up-sample once
             cu = c.unsqueeze(1)
             for j, s in enumerate(cfg.upsample_scales):
                 n = "upsample_conv.%d" % (2 * j)
@@ -238,7 +268,7 @@ def incremental_forward_ring(sd, c, T, u1, u2, cfg=WNConfig, test_inputs=None, l
             d = 2 ** (i % per)
             w = wn_weight(sd, p + "conv")                                        # (G, C, k) -> (G, k C): tap-major, as conv.py:53-57
             layers.append(dict(
-                d=d, ring=torch.zeros(B, (k - 1) * d + 1, cfg.residual_channels),
+                d=d, ring=torch.zeros(B, (k - 1) * d + 1, cfg.residual_channels, dtype=dt),
                 w=w.permute(0, 2, 1).reshape(w.shape[0], -1).contiguous(), b=sd[p + "conv.bias"],
                 wc=wn_weight(sd, p + "conv1x1c").reshape(cfg.gate_channels, -1) if cu is not None else None, bc=sd.get(p + "conv1x1c.bias"),
                 wg=wn_weight(sd, p + "conv1x1g").reshape(cfg.gate_channels, -1) if g_bc is not None else None, bg=sd.get(p + "conv1x1g.bias"),
@@ -246,22 +276,36 @@ def incremental_forward_ring(sd, c, T, u1, u2, cfg=WNConfig, test_inputs=None, l
                 ws=wn_weight(sd, p + "conv1x1_skip").reshape(cfg.skip_out_channels, -1), bs=sd[p + "conv1x1_skip.bias"]))
         w1 = wn_weight(sd, "last_conv_layers.1").reshape(cfg.skip_out_channels, -1)
         w2 = wn_weight(sd, "last_conv_layers.3").reshape(cfg.out_channels, -1)
-        out = torch.zeros(B, 1, T)
-        logits = torch.zeros(B, cfg.out_channels, T) if return_logits else None
-        cur = torch.zeros(B, 1)                                                  # initial input: zeros (wavenet.py:305-306)
+        out = torch.zeros(B, 1 if scalar else K, T, dtype=dt)
+        logits = torch.zeros(B, cfg.out_channels, T, dtype=dt) if return_logits else None
+        classes = torch.zeros(B, T, dtype=torch.int64)
+        if scalar:
+            cur = torch.zeros(B, 1, dtype=dt)                                    # initial input: zeros (wavenet.py:305-306)
+        elif initial_input is not None:
+            cur = initial_input.reshape(B, K)
+        else:
+            cur = F.one_hot(torch.full((B,), 127 if K > 127 else 0), K).to(dt)   # wavenet.py:308-312
+        if test_inputs is not None and not scalar and not torch.is_floating_point(test_inputs):
+            test_inputs = F.one_hot(test_inputs.long(), K).to(dt).transpose(1, 2)   # (B, n) classes -> (B, K, n) rows
         half = cfg.gate_channels // 2
         for t in range(T):
-            if test_inputs is not None and t < test_inputs.shape[-1]:
+            prev = out[:, :, t - 1].reshape(B, -1) if t > 0 else cur
+            if forced is not None:
+                cur = torch.where(forced[:, t].bool().reshape(B, 1), test_inputs[:, :, t].reshape(B, -1), prev)
+            elif test_inputs is not None and t < test_inputs.shape[-1]:
                 cur = test_inputs[:, :, t].reshape(B, -1)
             elif t > 0:
-                cur = out[:, :, t - 1].reshape(B, 1)
+                cur = prev
             h = F.linear(cur, w_first, sd["first_conv.bias"])                   # (B, C)
             skips = None
-            for L in layers:
+            for li, L in enumerate(layers):
                 ring = L["ring"]
                 ring[:, :-1] = ring[:, 1:].clone()                               # conv.py:39
                 ring[:, -1] = h
-                x = ring[:, ::L["d"]].reshape(B, -1)                             # conv.py:44: every d-th entry = the k taps
+                x = ring[:, ::L["d"]]                                            # conv.py:44: every d-th entry = the k taps
+                if tap_hook is not None:
+                    x = tap_hook(t, li, x)
+                x = x.reshape(B, -1)
                 y = F.linear(x, L["w"], L["b"])
                 a, b = y[:, :half], y[:, half:]
                 if L["wc"] is not None:
@@ -277,5 +321,13 @@ def incremental_forward_ring(sd, c, T, u1, u2, cfg=WNConfig, test_inputs=None, l
             y = F.linear(F.relu(F.linear(F.relu(skips), w1, sd["last_conv_layers.1.bias"])), w2, sd["last_conv_layers.3.bias"])
             if logits is not None:
                 logits[:, :, t] = y
-            out[:, 0, t] = mol_sample(y.unsqueeze(-1), u1[:, t:t + 1], u2[:, t:t + 1], log_scale_min)[:, 0]
-    return (out, logits) if return_logits else out
+            if scalar:
+                out[:, 0, t] = mol_sample(y.unsqueeze(-1), u1[:, t:t + 1], u2[:, t:t + 1], log_scale_min)[:, 0]
+            else:                                                                # wavenet.py:350-356
+                x = torch.softmax(y, dim=1) if softmax else y
+                if quantize:
+                    classes[:, t] = categorical_draw(x, u2[:, t])
+                    x = F.one_hot(classes[:, t], K).to(dt)
+                out[:, :, t] = x
+    res = classes if (return_classes and not scalar) else out
+    return (res, logits) if return_logits else res
