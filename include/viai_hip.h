@@ -460,6 +460,38 @@ int viai_wav_align(const float* wav, const int* a0, const int* a1, float* out, i
  * real, fake (B, 1, F, T) contiguous, mask (B, T), c (B, F, T) (the layout wavenet.py:291-299 up-samples).  Any F, T >= 1.                     */
 int viai_mel_compose(const float* real, const float* fake, const float* mask, float* c, int B, int F, int T, void* stream);
 
+/* ---- vocoder data preparation: waveform -> (signal, aligned row) per chunk (additive to ABI v20, csrc/preprocess.hip) ----
+ * `_process_utterance` of utils/librivox.py:44-117 behind the file decode.  A file wav (n_samples floats) is cut into n_chunks chunks
+ * [chunk_off[c], chunk_off[c] + chunk_len[c]) -- int32 arrays in DEVICE memory; the part of a chunk outside the file is ignored.  Each call is one
+ * launch for all chunks.  Rescaling: with amax != NULL -- a DEVICE float, max |wav| from viai_absmax -- every sample is taken as
+ * x / *amax * rescaling_max, an fp32 division and an fp32 multiplication each rounded on its own (numpy's float32 arithmetic, librivox.py:48-49);
+ * with amax == NULL samples are taken as they are.  mu = quantize_channels - 1.  Both refuse on the host, before any HIP call and so also on a
+ * machine without a device: a null pointer (amax excepted), n_chunks < 1, n_samples < 1 or above INT32_MAX, mu < 1; trim_bounds also thr < 0;
+ * pack also hop < 1, hop > fft, an unknown mode, max_len < 1, a capacity < 1 or above INT32_MAX, n_chunks > 65535.
+ *
+ * The silence trim (utils/audio.py:56-67 as librivox.py:66-73 calls it): with class(i) the mu-law class of sample i of the chunk -- computed on the
+ * fly by the device function of viai_mulaw_quantize, no class array is written -- and active(i) = |class(i) - silence_class| > thr,
+ *     bounds[c][0] = the first active i,                 chunk_len[c] if there is none
+ *     bounds[c][1] = the last active i among i >= 2,     -1 if there is none        (the reference's backward loop never looks at i = 0, 1)
+ * One block per chunk, integer min / max only: the same bits on every run.                                                                    */
+int viai_utt_trim_bounds(const float* wav, long n_samples, const int* chunk_off, const int* chunk_len, int n_chunks, const float* amax,
+                         float rescaling_max, int mu, int thr, int silence_class, int* bounds, void* stream);
+/* Given bounds[c] = (start, end), END EXCLUSIVE as in wav[start:end] (the sample at `end` is dropped, as the reference drops it), T = end - start:
+ *   rows[row_off[c] + i]      = sample start + i of the chunk, rescaled, i < T: what the mel front end reads.  With rows 16-byte aligned and
+ *                               row_off[c] % 4 == 0 a row starts 16-byte aligned (viai_stft_mel_route decides by the pointer's alignment) and is
+ *                               written with vector stores.
+ *   signal[sig_off[c] + j]    j < N hop, N = lws_num_frames(T, fft, hop): l = fft - hop pad values, the T samples, pad values up to N hop
+ *                               (lws_pad_lr and the cut of librivox.py:92-102) in the form `mode` names:
+ *       VIAI_UTT_MULAW_QUANTIZE  int32 classes of viai_mulaw_quantize, pad mu / 2;
+ *       VIAI_UTT_MULAW           floats y = sign(x) log1p(mu |x|) / log1p(mu), the same device function before its class step, pad 0.0;
+ *       VIAI_UTT_RAW             the floats themselves (with amax == NULL: bit for bit), pad 0.0.
+ * row_off, sig_off: int32 in device memory, in elements; rows_cap / signal_cap: elements the two buffers hold, no store goes beyond them.
+ * A chunk with end <= start writes nothing.  max_len (the longest chunk) sizes the grid only.                                                */
+enum { VIAI_UTT_MULAW_QUANTIZE = 0, VIAI_UTT_MULAW = 1, VIAI_UTT_RAW = 2 };
+int viai_utt_pack(const float* wav, long n_samples, const int* chunk_off, const int* chunk_len, const int* bounds, int n_chunks, int max_len,
+                  const float* amax, float rescaling_max, int mode, int mu, int fft, int hop, const int* row_off, float* rows, long rows_cap,
+                  const int* sig_off, void* signal, long signal_cap, void* stream);
+
 /* Incremental synthesis as ONE persistent launch (ABI v16, csrc/wavenet_pipe.hip): a weight-stationary pipeline for the reference-size
  * network (24 layers, 512 residual / 512 gate / 256 skip channels, 80 conditioning channels, 30 outputs, no global conditioning).  Every
  * stage owns compute units (10 per layer, 4 + 4 + 1 for the head) and keeps its weights in registers / LDS; the streams travel round the

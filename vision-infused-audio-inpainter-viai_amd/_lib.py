@@ -163,6 +163,8 @@ SIGNATURES = {
     "viai_gap_frame_mask": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "viai_wav_align": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "viai_mel_compose": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "viai_utt_trim_bounds": (_I, [_P, _L, _P, _P, _I, _P, _F, _I, _I, _I, _P, _P]),
+    "viai_utt_pack": (_I, [_P, _L, _P, _P, _P, _I, _I, _P, _F, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _P]),
     "viai_wn_categorical_ok": (_I, [C.POINTER(WnSynth)]),
     "viai_mulaw_decode": (_I, [_P, _P, _L, _I, _P]),
     "viai_mulaw_quantize": (_I, [_P, _P, _L, _I, _P]),

@@ -5,6 +5,7 @@
 // Activations are (B, 1, T, C) NHWC, i.e. (B*T) rows of C channels.
 #include "viai_common.h"
 #include "viai_internal.h"
+#include "viai_mulaw.h"
 
 namespace {
 
@@ -564,13 +565,7 @@ __global__ __launch_bounds__(256) void class_embed_bias_kernel(const float* __re
 // waveform -> mu-law class (utils/librivox.py:66-74)
 __global__ __launch_bounds__(256) void mulaw_quantize_kernel(const float* __restrict__ x, int* __restrict__ cls, long n, float mu) {
     const float l1p = log1pf(mu);
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
-        const float xx = x[i];
-        const float mag = log1pf(mu * fabsf(xx)) / l1p;              // a division: |x| = 1 gives exactly 1, class mu
-        const float y = xx < 0.f ? -mag : mag;
-        const int k = (int)((y + 1.f) * 0.5f * mu);                  // truncation
-        cls[i] = min(max(k, 0), (int)mu);
-    }
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) cls[i] = viai_mulaw_class(x[i], mu, l1p);   // viai_mulaw.h
 }
 
 __global__ __launch_bounds__(256) void scale_rows_kernel(float* __restrict__ d, const float* __restrict__ gscale, long n) {
