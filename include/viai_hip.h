@@ -569,6 +569,44 @@ int viai_stft_mel_banded(const float* wav, const float* window, const float* bas
  * which is device data (r512: <= 1024, wave: <= 2048; else they are read from global memory): not part of the answer.
  * family receives the NUL-terminated name (truncated to cap); returns 1, or 0 with an empty name where the entry point refuses.    */
 int viai_stft_mel_route(int n_samples, int fft, int hop, int n_mels, int wav_aligned8, char* family, int cap);
+/* The same stage on clips of DIFFERENT lengths in one call (fft = 1024; additive to ABI v20, no reference counterpart: the reference
+ * computes one mel per call).  Row r is the row_len[r] samples at wav + row_off[r]; rows may be packed back to back, leave gaps or
+ * overlap.  Every row is computed as a one-clip call of viai_stft_mel_banded on its own samples computes it, bit for bit: the zero padding
+ * on either side of a row is zero whatever lies next to it, its frame tiles start at its own frame 0, and it runs on the kernel family
+ * viai_stft_mel_route names for (row_len[r], fft, hop, n_mels, alignment of wav + row_off[r]).
+ *
+ * viai_stft_mel_ragged_plan -- host code only, no HIP call, no device needed -- turns row offsets and lengths into the tables:
+ *   in    row_off   [n_rows]      int64, samples from `wav`, >= 0
+ *         row_len   [n_rows]      int32, samples, 1 .. 2^29 - 1
+ *         base_aligned8           whether `wav` itself will be 8-byte aligned (row r is then aligned iff row_off[r] is even; with a base
+ *                                 4 bytes off, iff it is odd)
+ *   out   row_frames [n_rows]     frames of row r = lws_num_frames(row_len[r], fft, hop)
+ *         frame_off  [n_rows + 1] prefix sum of row_frames: row r owns output columns frame_off[r] .. frame_off[r + 1]
+ *         row_family [n_rows]     VIAI_STFT_R512 / _WAVE / _BANDED
+ *         items      [n][2]       int32 pairs (row, first frame of a tile), grouped by family in the order r512, wave, banded; inside a
+ *                                 family in row order, a row's tiles in frame order from frame 0.  A tile is 32 frames on r512 and wave,
+ *                                 8 on banded; the last tile of a row may be short.  Every (row, frame) is in exactly one tile.
+ *         family_items [3]        items of r512, wave, banded (their sum is n)
+ *   Any out pointer may be NULL.  Returns 0 when `items` was filled; the item count n (> 0) when items == NULL or item_cap < n (the
+ *   other outputs are written all the same: call with items = NULL to size the list); -1 where it refuses: n_rows < 1, a length
+ *   outside 1 .. 2^29 - 1, a negative offset, fft != 1024, a hop or n_mels viai_stft_mel_route refuses, more than 2^31 - 1 frames or
+ *   2^30 - 1 items in all.
+ *
+ * viai_stft_mel_ragged runs them: row_off, row_len, row_frames, frame_off and items are DEVICE copies of the arrays above (row_family
+ * stays on the host), family_items is the HOST array.  At most one launch per family present, persistent blocks over the family's items.
+ *   out, time_major == 0:  row r is a contiguous [n_mels][row_frames[r]] block at out + n_mels * frame_off[r]
+ *        time_major != 0:  one [frame_off[n_rows]][n_mels] array, row r at its rows frame_off[r] .. frame_off[r + 1]
+ *   Either way the call writes the n_mels * frame_off[n_rows] floats from `out` on and nothing else.
+ *   mask: NULL, or one float per output column, [frame_off[n_rows]]: column frame_off[r] + f scales frame f of row r (an fp32 product).
+ * Returns hipErrorInvalidValue before any launch on a NULL table or operand (mask excepted), n_rows < 1, no item, fft != 1024, or a
+ * family with items on a shape its kernel does not take.  The tables are trusted: hand in what the plan wrote.                      */
+enum { VIAI_STFT_R512 = 1, VIAI_STFT_WAVE = 2, VIAI_STFT_BANDED = 3 };
+long viai_stft_mel_ragged_plan(const long long* row_off, const int* row_len, int n_rows, int fft, int hop, int n_mels, int base_aligned8,
+                               int* row_frames, int* frame_off, int* row_family, int* items, long item_cap, int* family_items);
+int viai_stft_mel_ragged(const float* wav, const long long* row_off, const int* row_len, const int* row_frames, const int* frame_off,
+                         const int* items, const int* family_items, int n_rows, const float* window, const float* basis_t,
+                         const int* band_lo, const int* band_cnt, const float* mask, float* out, int fft, int hop, int n_mels,
+                         int time_major, float min_level_db, float ref_level_db, void* stream);
 
 /* -------------------------------------------------- callers either side of the path
  * Batch assembly on the device, Data_loaders/audio_loader.py:185-245: frames uint8 [n][S][S][C] (RGB or

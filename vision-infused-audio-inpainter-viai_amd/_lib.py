@@ -186,6 +186,8 @@ SIGNATURES = {
     "viai_stft_mel": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P]),
     "viai_stft_mel_banded": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P]),
     "viai_stft_mel_route": (_I, [_I, _I, _I, _I, _I, C.c_char_p, _I]),
+    "viai_stft_mel_ragged_plan": (_L, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
+    "viai_stft_mel_ragged": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
     "viai_conv2d_pack_job": (_I, [_CP, _I, _P, _P, C.POINTER(PackJob)]),
     "viai_pack_jobs_run": (_I, [_P, _I, _I, _P]),
     "viai_frames_prep": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _I, _P]),

@@ -103,6 +103,118 @@ class MelFrontEnd:
                                          c.num_mels, frames, float(c.min_level_db), float(c.ref_level_db), st), "viai_stft_mel")
         return out
 
+    def ragged(self, wav, lengths=None, offsets=None, mask=None, time_major=False):
+        """Mel of clips of DIFFERENT lengths in one call (`viai_stft_mel_ragged`, table layout in include/viai_hip.h).
+
+        wav: a 1-D fp32 GPU tensor holding the rows, with `lengths` (host ints, >= 1 each) and optionally `offsets` (host ints, in samples; default:
+        the rows packed back to back) -- rows must lie inside `wav`, may leave gaps and may overlap; or a list of 1-D GPU tensors, which this method
+        packs into one buffer at offsets that are multiples of 4 samples, so that even-length rows take the r512 route.
+        mask: optional, flat, one float per output frame of all rows in row order (sum of the rows' frame counts).
+        -> a list of per-row tensors, views of ONE allocation, each contiguous: (num_mels, frames_r), or (frames_r, num_mels) with time_major.
+
+        Row r gets the bits of `self(row_r[None])[0, 0]` on a row whose first sample is aligned as this one's is (8-byte aligned or not: the kernel
+        family is chosen per row by length and alignment, as `viai_stft_mel_route` reports): for rows at even offsets of an aligned buffer, and for a
+        list of tensors, that is the result on a fresh copy of the row.  No device-to-host read; one table upload and one C call.
+        For fft_size != 1024, where only the dense one-frame-per-block kernel exists, and with `force_dense`, the method loops over the rows with
+        `__call__` and copies each result into the shared allocation."""
+        c = self.cfg
+        fft, hop, n_mels = int(c.fft_size), int(c.hop_size), int(c.num_mels)
+        if hop < 1 or hop > fft or n_mels < 1:
+            raise ValueError("MelFrontEnd.ragged: 1 <= hop_size <= fft_size and num_mels >= 1")
+        packed = isinstance(wav, (list, tuple))
+        if packed:
+            if lengths is not None or offsets is not None:
+                raise ValueError("MelFrontEnd.ragged: a list of rows carries its own lengths; lengths / offsets go with a 1-D buffer")
+            if len(wav) == 0:
+                raise ValueError("MelFrontEnd.ragged: no row")
+            if any(not isinstance(t, torch.Tensor) or t.dim() != 1 for t in wav):
+                raise ValueError("MelFrontEnd.ragged: every row is an (n,) tensor")
+            lengths = [int(t.numel()) for t in wav]
+            offsets, o = [], 0
+            for n in lengths:
+                offsets.append(o)
+                o += (n + 3) // 4 * 4
+            span = o
+            tensors = list(wav)
+        else:
+            if not isinstance(wav, torch.Tensor) or wav.dim() != 1:
+                raise ValueError("MelFrontEnd.ragged: wav is an (n,) tensor or a list of them")
+            if lengths is None:
+                raise ValueError("MelFrontEnd.ragged: a 1-D buffer needs the rows' lengths")
+            lengths = [int(n) for n in lengths]
+            if len(lengths) == 0:
+                raise ValueError("MelFrontEnd.ragged: no row")
+            if offsets is None:
+                offsets, o = [], 0
+                for n in lengths:
+                    offsets.append(o)
+                    o += n
+            offsets = [int(o) for o in offsets]
+            if len(offsets) != len(lengths):
+                raise ValueError("MelFrontEnd.ragged: %d lengths but %d offsets" % (len(lengths), len(offsets)))
+            span = int(wav.numel())
+            tensors = [wav]
+        for r, (o, n) in enumerate(zip(offsets, lengths)):
+            if n < 1:
+                raise ValueError("MelFrontEnd.ragged: row %d has length %d; the front end needs at least one sample" % (r, n))
+            if n > 2 ** 29 - 1:
+                raise ValueError("MelFrontEnd.ragged: row %d has %d samples, more than the kernels' 2^29 - 1" % (r, n))
+            if o < 0 or o + n > span:
+                raise ValueError("MelFrontEnd.ragged: row %d (samples %d to %d) does not lie inside the %d samples of wav" % (r, o, o + n, span))
+        nr = len(lengths)
+        frames = [lws_num_frames(n, fft, hop) for n in lengths]
+        total = sum(frames)
+        if total > 2 ** 31 - 1:
+            raise ValueError("MelFrontEnd.ragged: %d frames do not fit the kernels' int32 indices" % total)
+        if mask is not None and (not isinstance(mask, torch.Tensor) or mask.numel() != total):
+            raise ValueError("MelFrontEnd.ragged: mask holds one value per output frame (%d)" % total)
+        if any(not t.is_cuda for t in tensors) or (mask is not None and not mask.is_cuda):
+            raise _lib.ViaiLibraryError("MelFrontEnd runs on the GPU only; no CPU fallback")
+        lib = _lib.load()
+        dev = tensors[0].device
+        if packed:
+            buf = torch.zeros(span, dtype=torch.float32, device=dev)
+            for t, o, n in zip(tensors, offsets, lengths):
+                buf[o:o + n].copy_(t)
+        else:
+            buf = wav.contiguous().float()
+        m = None if mask is None else mask.reshape(-1).contiguous().float()
+        out = torch.empty(n_mels * total, dtype=torch.float32, device=dev)
+        fo = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+        shape = (lambda f: (f, n_mels)) if time_major else (lambda f: (n_mels, f))
+        views = [out[n_mels * int(fo[r]):n_mels * int(fo[r + 1])].view(shape(frames[r])) for r in range(nr)]
+        if fft != 1024 or getattr(self, "force_dense", False):
+            for r in range(nr):
+                one = self(buf[offsets[r]:offsets[r] + lengths[r]][None], None if m is None else m[int(fo[r]):int(fo[r + 1])][None])[0, 0]
+                views[r].copy_(one.t() if time_major else one)
+            return views
+        # the tables, one int32 host buffer: row_off (int64) | row_len | row_frames | frame_off | items
+        head = np.empty(5 * nr + 1, dtype=np.int32)
+        head[:2 * nr].view(np.int64)[:] = offsets
+        head[2 * nr:3 * nr] = lengths
+        fam_items = np.zeros(3, dtype=np.int32)
+        al = int(buf.data_ptr() % 8 == 0)
+
+        def plan(tab, n_items):
+            p = tab.ctypes.data
+            return lib.viai_stft_mel_ragged_plan(p, p + 8 * nr, nr, fft, hop, n_mels, al, p + 12 * nr, p + 16 * nr, None,
+                                                 p + 4 * (5 * nr + 1) if n_items else None, n_items, fam_items.ctypes.data)
+        need = plan(head, 0)
+        if need < 1:
+            raise ValueError("MelFrontEnd.ragged: viai_stft_mel_ragged_plan refuses these rows at fft %d, hop %d, %d bands" % (fft, hop, n_mels))
+        tab = np.empty(5 * nr + 1 + 2 * need, dtype=np.int32)
+        tab[:3 * nr] = head[:3 * nr]
+        if plan(tab, need) != 0 or tab[3 * nr:4 * nr].tolist() != frames:
+            raise _lib.ViaiLibraryError("viai_stft_mel_ragged_plan disagrees with lws_num_frames")
+        d = torch.from_numpy(tab).to(dev)
+        p = d.data_ptr()
+        _lib.check(lib.viai_stft_mel_ragged(buf.data_ptr(), p, p + 8 * nr, p + 12 * nr, p + 16 * nr, p + 4 * (5 * nr + 1), fam_items.ctypes.data, nr,
+                                            self.window.data_ptr(), self.basis_t.data_ptr(), self.band_lo.data_ptr(), self.band_cnt.data_ptr(),
+                                            0 if m is None else m.data_ptr(), out.data_ptr(), fft, hop, n_mels, int(bool(time_major)),
+                                            float(c.min_level_db), float(c.ref_level_db), torch.cuda.current_stream().cuda_stream),
+                   "viai_stft_mel_ragged")
+        return views
+
 
 def inv_mel_amplitude(S, min_level_db=None):
     """`_db_to_amp(_denormalize(S))` of utils/audio.py:135-144 in one pass: the normalised mel the generator emits

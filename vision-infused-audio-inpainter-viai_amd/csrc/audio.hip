@@ -82,22 +82,37 @@ __global__ __launch_bounds__(256) void stft_mel_kernel(const float* __restrict__
 constexpr int SB_F = 8;                       // frames per block
 constexpr int SB_N = 1024;
 
-__global__ __launch_bounds__(256) void stft_mel_banded_kernel(const float* __restrict__ wav, const float* __restrict__ window,
-                                                              const float* __restrict__ basis_t, const int* __restrict__ band_lo,
-                                                              const int* __restrict__ band_cnt, const float* __restrict__ mask,
-                                                              float* __restrict__ mel, int n_samples, int hop, int n_mels,
-                                                              int frames, float min_db, float ref_db) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_a[];
-    float2* bufA = reinterpret_cast<float2*>(smem_a);                         // [4][1024]
-    float2* bufB = bufA + 4 * SB_N;                                           // [4][1024]
-    float2* tw = bufB + 4 * SB_N;                                             // [768]  exp(-2 pi i n / 1024)
-    const int tid = threadIdx.x, clip = blockIdx.y, f0 = blockIdx.x * SB_F;
-    const float* y = wav + (size_t)clip * n_samples;
-    for (int n = tid; n < 768; n += 256) {
-        float s, c;
-        sincospif(-(float)n * (1.0f / 512.0f), &s, &c);
-        tw[n] = make_float2(c, s);
-    }
+// Ragged launches (viai_stft_mel_ragged): every clip ("row") has its own first sample, length, frame count and first output column, and a work item is a
+// (row, first frame of a tile) pair from a list the host planned (viai_stft_mel_ragged_plan; table layout in include/viai_hip.h).  The three fft = 1024 kernels
+// below take the tables as their RG = true form: only the prologue of an item (where its samples are, how many) and the store (where its columns go) differ, the
+// arithmetic of a frame is the uniform kernel's.  A tile starts at the row's frame 0, as in a one-clip launch, so frame f of a row sits in the same wave and the
+// same lane group as there: the same bits.  A uniform launch passes an empty table.
+struct RagTab {
+    const long long* row_off;   // [n_rows] first sample of the row in `wav`
+    const int* row_len;         // [n_rows] samples
+    const int* row_frames;      // [n_rows] frames
+    const int* frame_off;       // [n_rows + 1] first output column of the row (prefix sum of row_frames)
+    const int* items;           // [n_items][2] (row, first frame); the launch's own slice of the list
+    int time_major;             // 0: row r is an [n_mels][frames_r] block at n_mels frame_off[r]; 1: [total frames][n_mels]
+};
+struct RagItem { const float* y; int ns, fr, fo, F0; };
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// item gi of the list (gi is block-uniform); every field in SGPRs: the buffer descriptors built from them must be scalar
+__device__ __forceinline__ RagItem rag_item(const RagTab& rt, const float* wav, int gi) {
+    const int row = uni(rt.items[2 * gi]);
+    const long long off = rt.row_off[row];
+    const long long offu = (long long)(((unsigned long long)(unsigned)uni((int)(off >> 32)) << 32) | (unsigned)uni((int)off));
+    return RagItem{wav + offu, uni(rt.row_len[row]), uni(rt.row_frames[row]), uni(rt.frame_off[row]), uni(rt.items[2 * gi + 1])};
+}
+
+// frames f0 .. f0 + 7 of ONE clip: y its first sample, n_samples / frames its own, mrow its mask (or null), band m of frame f goes to dst[m sm + f sf].
+// RG (ragged): scalar stores only (a row's block starts wherever the rows before it end).  tw is filled by the caller; a barrier follows its fill in here.
+template <bool RG>
+__device__ __forceinline__ void stft_banded_tile(float2* bufA, float2* bufB, const float2* tw, const float* __restrict__ y, const float* __restrict__ window,
+                                                 const float* __restrict__ basis_t, const int* __restrict__ band_lo, const int* __restrict__ band_cnt,
+                                                 const float* __restrict__ mrow, float* __restrict__ dst0, size_t sm, size_t sf, int n_samples, int hop, int n_mels,
+                                                 int frames, int f0, float min_db, float ref_db) {
+    const int tid = threadIdx.x;
     // windowed frames: FFT q holds frame f0 + 2 q (real part) and f0 + 2 q + 1 (imaginary part); frames past the end are zero
     for (int j = tid; j < SB_N; j += 256) {
         const float w = window[j];
@@ -166,18 +181,69 @@ __global__ __launch_bounds__(256) void stft_mel_banded_kernel(const float* __res
             const float S = 20.f * log10f(fmaxf(min_level, acc[f])) - ref_db;
             float nrm = (S - min_db) / (-min_db);
             nrm = fminf(fmaxf(nrm, 0.f), 1.f);
-            const float mk = (mask && f0 + f < frames) ? mask[(size_t)clip * frames + f0 + f] : 1.f;
+            const float mk = (mrow && f0 + f < frames) ? mrow[f0 + f] : 1.f;
             r[f] = nrm * mk;
         }
-        float* dst = mel + ((size_t)clip * n_mels + m) * frames + f0;
-        if (vec_ok) {
-            *reinterpret_cast<f32x4*>(dst) = f32x4{r[0], r[1], r[2], r[3]};
-            *reinterpret_cast<f32x4*>(dst + 4) = f32x4{r[4], r[5], r[6], r[7]};
-        } else {
+        if constexpr (RG) {
+            float* dst = dst0 + (size_t)m * sm + (size_t)f0 * sf;
 #pragma unroll
             for (int f = 0; f < SB_F; ++f)
-                if (f0 + f < frames) dst[f] = r[f];
+                if (f0 + f < frames) dst[(size_t)f * sf] = r[f];
+        } else {
+            float* dst = dst0 + (size_t)m * frames + f0;
+            if (vec_ok) {
+                *reinterpret_cast<f32x4*>(dst) = f32x4{r[0], r[1], r[2], r[3]};
+                *reinterpret_cast<f32x4*>(dst + 4) = f32x4{r[4], r[5], r[6], r[7]};
+            } else {
+#pragma unroll
+                for (int f = 0; f < SB_F; ++f)
+                    if (f0 + f < frames) dst[f] = r[f];
+            }
         }
+    }
+}
+
+__device__ __forceinline__ void stft_banded_twiddles(float2* tw) {
+    for (int n = threadIdx.x; n < 768; n += 256) {
+        float s, c;
+        sincospif(-(float)n * (1.0f / 512.0f), &s, &c);
+        tw[n] = make_float2(c, s);
+    }
+}
+
+__global__ __launch_bounds__(256) void stft_mel_banded_kernel(const float* __restrict__ wav, const float* __restrict__ window,
+                                                              const float* __restrict__ basis_t, const int* __restrict__ band_lo,
+                                                              const int* __restrict__ band_cnt, const float* __restrict__ mask,
+                                                              float* __restrict__ mel, int n_samples, int hop, int n_mels,
+                                                              int frames, float min_db, float ref_db) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_a[];
+    float2* bufA = reinterpret_cast<float2*>(smem_a);                         // [4][1024]
+    float2* bufB = bufA + 4 * SB_N;                                           // [4][1024]
+    float2* tw = bufB + 4 * SB_N;                                             // [768]  exp(-2 pi i n / 1024)
+    const int clip = blockIdx.y;
+    stft_banded_twiddles(tw);
+    stft_banded_tile<false>(bufA, bufB, tw, wav + (size_t)clip * n_samples, window, basis_t, band_lo, band_cnt, mask ? mask + (size_t)clip * frames : nullptr,
+                            mel + (size_t)clip * n_mels * frames, 0, 0, n_samples, hop, n_mels, frames, blockIdx.x * SB_F, min_db, ref_db);
+}
+
+// the ragged form: persistent blocks over the item list, one eight-frame tile of one row per item
+__global__ __launch_bounds__(256) void stft_mel_banded_ragged_kernel(const float* __restrict__ wav, const float* __restrict__ window,
+                                                                     const float* __restrict__ basis_t, const int* __restrict__ band_lo,
+                                                                     const int* __restrict__ band_cnt, const float* __restrict__ mask,
+                                                                     float* __restrict__ mel, int n_items, int hop, int n_mels, float min_db, float ref_db,
+                                                                     RagTab rt) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_a[];
+    float2* bufA = reinterpret_cast<float2*>(smem_a);
+    float2* bufB = bufA + 4 * SB_N;
+    float2* tw = bufB + 4 * SB_N;
+    stft_banded_twiddles(tw);
+    for (int gi = blockIdx.x; gi < n_items; gi += gridDim.x) {
+        const RagItem it = rag_item(rt, wav, gi);
+        float* dst0 = mel + (size_t)n_mels * it.fo;                           // either layout: the row's block starts n_mels frame_off[row] floats in
+        const size_t sm = rt.time_major ? 1 : (size_t)it.fr, sf = rt.time_major ? (size_t)n_mels : 1;
+        stft_banded_tile<true>(bufA, bufB, tw, it.y, window, basis_t, band_lo, band_cnt, mask ? mask + it.fo : nullptr, dst0, sm, sf, it.ns, hop, n_mels,
+                               it.fr, it.F0, min_db, ref_db);
+        __syncthreads();                                                      // the magnitudes live in a frame buffer the next item refills
     }
 }
 
@@ -262,12 +328,13 @@ struct SwCfg {
     static constexpr int FPI = 2 * NW, OT = TF + 1, NT = 64 * NW, FH = FPI / 8;
     static constexpr int lds = NW * SW_WREG * 8 + 516 * MP * 4 + WCAP * 4 + (MMAX + 8) * 4 + 64 * 8 + SW_OMEL * OT * 4;
 };
-template <int SW_NW, int SW_TF, int SW_MP, int SW_WCAP, int SW_MMAX>
+// RG: the ragged form -- n_clips counts ITEMS of rt.items (one SW_TF-frame tile of one row each), n_samples and frames are unused.
+template <int SW_NW, int SW_TF, int SW_MP, int SW_WCAP, int SW_MMAX, bool RG>
 __global__ __launch_bounds__(64 * SW_NW) __attribute__((amdgpu_waves_per_eu(2))) void stft_mel_wave_kernel(const float* __restrict__ wav, const float* __restrict__ window,
                                                             const float* __restrict__ basis_t, const int* __restrict__ band_lo,
                                                             const int* __restrict__ band_cnt, const float* __restrict__ mask,
                                                             float* __restrict__ mel, int n_clips, int n_samples, int hop, int n_mels,
-                                                            int frames, float min_db, float ref_db) {
+                                                            int frames, float min_db, float ref_db, RagTab rt) {
     constexpr int SW_FPI = 2 * SW_NW, SW_OT = SW_TF + 1, SW_FH = SW_FPI / 8;      // SW_FH: eight-frame halves of an iteration (a mel item = (band, half))
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_w[];
     constexpr int NT = 64 * SW_NW;
@@ -313,7 +380,7 @@ __global__ __launch_bounds__(64 * SW_NW) __attribute__((amdgpu_waves_per_eu(2)))
     const int m_0 = own_0 ? tid / SW_FH : 0, hf_0 = tid % SW_FH;
     const int lo_0 = own_0 ? band_lo[m_0] : 0, cnt_0 = own_0 ? band_cnt[m_0] : 0, o_0 = boff[m_0];
     const int cmax_0 = wave_max_i(cnt_0);
-    const int gpc = (frames + SW_TF - 1) / SW_TF, total = n_clips * gpc;                   // super-groups of 32 frames
+    const int gpc = RG ? 1 : (frames + SW_TF - 1) / SW_TF, total = n_clips * gpc;          // super-groups of 32 frames
     const int per = (total + gridDim.x - 1) / gridDim.x;
     const int g_end = min(total, (int)(blockIdx.x + 1) * per);
     __syncthreads();
@@ -324,13 +391,21 @@ __global__ __launch_bounds__(64 * SW_NW) __attribute__((amdgpu_waves_per_eu(2)))
     // padding needs no test either; a frame past the end (or an iteration past the block's range) gets an empty descriptor.
     float ra[16], rb[16];
     auto request = [&](int gi, int sub) {
-        const int clip = gi / gpc, f0 = (gi - clip * gpc) * SW_TF + sub * SW_FPI;
-        const float* y = wav + (size_t)clip * n_samples;
+        const bool live = gi < g_end;
+        const float* y;
+        int ns, fr, f0;
+        if constexpr (RG) {                                                                // the row's own base and length: a neighbour packed against it is out of range
+            const RagItem it = rag_item(rt, wav, live ? gi : g_end - 1);                   // (an item past the block's range is never read from the list)
+            y = it.y; ns = it.ns; fr = it.fr; f0 = it.F0 + sub * SW_FPI;
+        } else {
+            const int clip = gi / gpc;
+            y = wav + (size_t)clip * n_samples; ns = n_samples; fr = frames; f0 = (gi - clip * gpc) * SW_TF + sub * SW_FPI;
+        }
         const int fa = f0 + 2 * w;
         const int ia = fa * hop - (1024 - hop), ib = ia + hop;
-        const bool live = gi < g_end, va = live && fa < frames, vb = live && fa + 1 < frames;
-        const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, va ? n_samples * 4 : 0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, vb ? n_samples * 4 : 0, 0x00020000);
+        const bool va = live && fa < fr, vb = live && fa + 1 < fr;
+        const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, va ? ns * 4 : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, vb ? ns * 4 : 0, 0x00020000);
         const int oa = (ia + n2) * 4, ob = (ib + n2) * 4;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -340,7 +415,26 @@ __global__ __launch_bounds__(64 * SW_NW) __attribute__((amdgpu_waves_per_eu(2)))
     };
     if ((int)(blockIdx.x * per) < g_end) request(blockIdx.x * per, 0);
     for (int gi = blockIdx.x * per; gi < g_end; ++gi) {
-        const int clip = gi / gpc, F0 = (gi - clip * gpc) * SW_TF;
+        // the clip of this tile: its frame count, the tile's first frame, the clip's mask, and where band m of frame f goes (obase[m osm + f osf])
+        int fr_, F0_;
+        const float* mrow = nullptr;
+        float* obase;
+        size_t osm, osf = 1;
+        if constexpr (RG) {
+            const RagItem it = rag_item(rt, wav, gi);
+            fr_ = it.fr; F0_ = it.F0;
+            if (mask != nullptr) mrow = mask + it.fo;
+            obase = mel + (size_t)n_mels * it.fo;
+            osm = rt.time_major ? 1 : (size_t)it.fr;
+            osf = rt.time_major ? (size_t)n_mels : 1;
+        } else {
+            const int clip = gi / gpc;
+            fr_ = frames; F0_ = (gi - clip * gpc) * SW_TF;
+            if (mask != nullptr) mrow = mask + (size_t)clip * frames;
+            obase = mel + (size_t)clip * n_mels * frames;
+            osm = (size_t)frames;
+        }
+        const int frames = fr_, F0 = F0_;                                                  // (shadows the parameter from here on: the row's own count in the ragged form)
         for (int sub = 0; sub < SW_TF / SW_FPI; ++sub) {
             const int f0 = F0 + sub * SW_FPI;
             if (f0 >= frames) break;                                                       // (uniform)
@@ -408,7 +502,7 @@ __global__ __launch_bounds__(64 * SW_NW) __attribute__((amdgpu_waves_per_eu(2)))
 #pragma unroll
                 for (int f = 0; f < 8; ++f) mk[f] = 1.f;
                 if (mask != nullptr) {                                                            // (uniform) requested before the walk; frames past the end read as zero and are not stored
-                    const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void*)(mask + (size_t)clip * frames), 0, frames * 4, 0x00020000);
+                    const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void*)mrow, 0, frames * 4, 0x00020000);
 #pragma unroll
                     for (int f = 0; f < 8; ++f) mk[f] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_m, (fb + f) * 4, 0, 0));
                 }
@@ -440,18 +534,27 @@ __global__ __launch_bounds__(64 * SW_NW) __attribute__((amdgpu_waves_per_eu(2)))
                         float nrm = (S - min_db) * inv_mdb;
                         nrm = fminf(fmaxf(nrm, 0.f), 1.f);
                         if (tiled) otile[m * SW_OT + (fb - F0) + f] = nrm * mk[f];
-                        else if (fb + f < frames) mel[((size_t)clip * n_mels + m) * frames + fb + f] = nrm * mk[f];
+                        else if (fb + f < frames) obase[(size_t)m * osm + (size_t)(fb + f) * osf] = nrm * mk[f];
                     }
                 }
             }
             __syncthreads();                                                               // the magnitude table is rewritten by the next iteration
         }
         if (tiled) {
-            // the tile's rows out as runs of up to 32 consecutive frames: lane = frame, two bands per wave instruction
             const int nf = min(SW_TF, frames - F0);
-            for (int idx = tid; idx < n_mels * SW_TF; idx += NT) {
-                const int m = idx / SW_TF, f = idx % SW_TF;
-                if (f < nf) mel[((size_t)clip * n_mels + m) * frames + F0 + f] = otile[m * SW_OT + f];
+            if (RG && rt.time_major) {
+                // frame-major output: the tile's nf frames are ONE contiguous run of nf n_mels floats; lane = band, read down the tile's columns (stride SW_OT: no conflicts)
+                float* dst = obase + (size_t)F0 * n_mels;
+                for (int idx = tid; idx < nf * n_mels; idx += NT) {
+                    const int f = idx / n_mels, m = idx - f * n_mels;
+                    dst[idx] = otile[m * SW_OT + f];
+                }
+            } else {
+                // the tile's rows out as runs of up to 32 consecutive frames: lane = frame, two bands per wave instruction
+                for (int idx = tid; idx < n_mels * SW_TF; idx += NT) {
+                    const int m = idx / SW_TF, f = idx % SW_TF;
+                    if (f < nf) obase[(size_t)m * osm + F0 + f] = otile[m * SW_OT + f];
+                }
             }
             __syncthreads();
         }
@@ -488,11 +591,12 @@ __device__ __forceinline__ void dft8(c32 (&v)[8]) {
 }
 __device__ __forceinline__ float lane_from(float x, int src_lane) { return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src_lane * 4, __builtin_bit_cast(int, x))); }
 
-template <int R5_NW, int R5_TF, int R5_MP, int R5_ROW2>
+// RG: the ragged form, as on the kernel above (n_clips counts items; every row of an r512 item has an even length and an 8-byte aligned first sample)
+template <int R5_NW, int R5_TF, int R5_MP, int R5_ROW2, bool RG>
 __global__ __launch_bounds__(64 * R5_NW) __attribute__((amdgpu_waves_per_eu(4))) void stft_mel_r512_kernel(const float* __restrict__ wav, const float* __restrict__ window, const float* __restrict__ basis_t,
                                                                     const int* __restrict__ band_lo, const int* __restrict__ band_cnt, const float* __restrict__ mask,
                                                                     float* __restrict__ mel, int n_clips, int n_samples, int hop, int n_mels, int frames,
-                                                                    float min_db, float ref_db) {
+                                                                    float min_db, float ref_db, RagTab rt) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_r[];
     constexpr int NT = 64 * R5_NW, R5_OT = R5_TF + 1, QN = R5_NW / 4;                // QN: four-frame quarters of an iteration (a mel item = (band, quarter))
     c32* ebuf = reinterpret_cast<c32*>(smem_r);                                   // [16 waves][R5_WREG]
@@ -529,7 +633,7 @@ __global__ __launch_bounds__(64 * R5_NW) __attribute__((amdgpu_waves_per_eu(4)))
     const c32 wk0 = {cs0, sn0};                                                            // W1024^lane; W1024^(lane + 64 ka) = wk0 W16^ka
     const float min_level = exp10f(min_db / 20.f), inv_mdb = -1.f / min_db;
     c32* E = ebuf + w * R5_WREG;
-    const int gpc = (frames + R5_TF - 1) / R5_TF, total = n_clips * gpc;
+    const int gpc = RG ? 1 : (frames + R5_TF - 1) / R5_TF, total = n_clips * gpc;
     const int per = (total + gridDim.x - 1) / gridDim.x;
     const int g_end = min(total, (int)(blockIdx.x + 1) * per);
     // a thread's mel item: band tid / QN, frames 4 (tid % QN) .. + 4 of the iteration's
@@ -540,8 +644,26 @@ __global__ __launch_bounds__(64 * R5_NW) __attribute__((amdgpu_waves_per_eu(4)))
     const int partner = (64 - lane) & 63;
     __syncthreads();
     for (int gi = blockIdx.x * per; gi < g_end; ++gi) {
-        const int clip = gi / gpc, F0 = (gi - clip * gpc) * R5_TF;
-        const float* y = wav + (size_t)clip * n_samples;
+        // the clip of this tile: its first sample, length and frame count, the tile's first frame, the clip's mask, and where band m of frame f goes
+        int ns_, fr_, F0_;
+        const float* y;
+        const float* mrow = nullptr;
+        float* obase;
+        size_t osm;
+        if constexpr (RG) {
+            const RagItem it = rag_item(rt, wav, gi);
+            y = it.y; ns_ = it.ns; fr_ = it.fr; F0_ = it.F0;
+            if (mask != nullptr) mrow = mask + it.fo;
+            obase = mel + (size_t)n_mels * it.fo;
+            osm = (size_t)it.fr;
+        } else {
+            const int clip = gi / gpc;
+            y = wav + (size_t)clip * n_samples; ns_ = n_samples; fr_ = frames; F0_ = (gi - clip * gpc) * R5_TF;
+            if (mask != nullptr) mrow = mask + (size_t)clip * frames;
+            obase = mel + (size_t)clip * n_mels * frames;
+            osm = (size_t)frames;
+        }
+        const int n_samples = ns_, frames = fr_, F0 = F0_;                                 // (shadow the parameters from here on: the row's own in the ragged form)
         for (int sub = 0; sub < R5_TF / R5_NW; ++sub) {
             const int f0 = F0 + sub * R5_NW;
             if (f0 >= frames) break;                                                       // (uniform)
@@ -611,7 +733,7 @@ __global__ __launch_bounds__(64 * R5_NW) __attribute__((amdgpu_waves_per_eu(4)))
                 const int fb = f0 + qf * 4;
                 float mk[4] = {1.f, 1.f, 1.f, 1.f};
                 if (mask != nullptr) {
-                    const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void*)(mask + (size_t)clip * frames), 0, frames * 4, 0x00020000);
+                    const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void*)mrow, 0, frames * 4, 0x00020000);
 #pragma unroll
                     for (int f = 0; f < 4; ++f) mk[f] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_m, (fb + f) * 4, 0, 0));
                 }
@@ -646,37 +768,46 @@ __global__ __launch_bounds__(64 * R5_NW) __attribute__((amdgpu_waves_per_eu(4)))
             __syncthreads();                                                               // the magnitude table is rewritten by the next iteration
         }
         const int nf = min(R5_TF, frames - F0);
-        for (int idx = tid; idx < n_mels * R5_TF; idx += NT) {
-            const int m = idx / R5_TF, f = idx % R5_TF;
-            if (f < nf) mel[((size_t)clip * n_mels + m) * frames + F0 + f] = otile[m * R5_OT + f];
+        if (RG && rt.time_major) {                                                         // (as in the wave kernel: one contiguous run of nf n_mels floats)
+            float* dst = obase + (size_t)F0 * n_mels;
+            for (int idx = tid; idx < nf * n_mels; idx += NT) {
+                const int f = idx / n_mels, m = idx - f * n_mels;
+                dst[idx] = otile[m * R5_OT + f];
+            }
+        } else {
+            for (int idx = tid; idx < n_mels * R5_TF; idx += NT) {
+                const int m = idx / R5_TF, f = idx % R5_TF;
+                if (f < nf) obase[(size_t)m * osm + F0 + f] = otile[m * R5_OT + f];
+            }
         }
         __syncthreads();
     }
 }
 
-template <int NW, int TF, int MP, int ROW2>
+// RG: the ragged form -- B counts the items of rt.items, n_samples and frames are unused (every item is one tile)
+template <int NW, int TF, int MP, int ROW2, bool RG = false>
 int launch_stft_r512(int per_cu, const float* wav, const float* window, const float* basis_t, const int* band_lo, const int* band_cnt, const float* mask, float* mel,
-                     int B, int n_samples, int hop, int n_mels, int frames, float min_db, float ref_db, hipStream_t st) {
+                     int B, int n_samples, int hop, int n_mels, int frames, float min_db, float ref_db, hipStream_t st, RagTab rt = RagTab{}) {
     constexpr int lds = r5_lds<NW, TF, MP>();
-    auto kern = stft_mel_r512_kernel<NW, TF, MP, ROW2>;
+    auto kern = stft_mel_r512_kernel<NW, TF, MP, ROW2, RG>;
     static bool attr = false;
     if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; }
-    const long groups = (long)B * ((frames + TF - 1) / TF);
+    const long groups = RG ? (long)B : (long)B * ((frames + TF - 1) / TF);
     const int grid = (int)(groups < 256 * per_cu ? groups : 256 * per_cu);
-    VIAI_LAUNCH(kern, dim3(grid), dim3(64 * NW), lds, st, wav, window, basis_t, band_lo, band_cnt, mask, mel, B, n_samples, hop, n_mels, frames, min_db, ref_db);
+    VIAI_LAUNCH(kern, dim3(grid), dim3(64 * NW), lds, st, wav, window, basis_t, band_lo, band_cnt, mask, mel, B, n_samples, hop, n_mels, frames, min_db, ref_db, rt);
     return viai_launch_status();
 }
 
-template <int NW, int TF, int MP, int WCAP, int MMAX>
+template <int NW, int TF, int MP, int WCAP, int MMAX, bool RG = false>
 int launch_stft_wave(int per_cu, const float* wav, const float* window, const float* basis_t, const int* band_lo, const int* band_cnt, const float* mask, float* mel,
-                     int B, int n_samples, int hop, int n_mels, int frames, float min_db, float ref_db, hipStream_t st) {
+                     int B, int n_samples, int hop, int n_mels, int frames, float min_db, float ref_db, hipStream_t st, RagTab rt = RagTab{}) {
     using Cfg = SwCfg<NW, TF, MP, WCAP, MMAX>;
-    auto kern = stft_mel_wave_kernel<NW, TF, MP, WCAP, MMAX>;
+    auto kern = stft_mel_wave_kernel<NW, TF, MP, WCAP, MMAX, RG>;
     static bool attr = false;
     if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::lds); attr = true; }
-    const long groups = (long)B * ((frames + TF - 1) / TF);
+    const long groups = RG ? (long)B : (long)B * ((frames + TF - 1) / TF);
     const int grid = (int)(groups < 256 * per_cu ? groups : 256 * per_cu);      // persistent blocks
-    VIAI_LAUNCH(kern, dim3(grid), dim3(Cfg::NT), Cfg::lds, st, wav, window, basis_t, band_lo, band_cnt, mask, mel, B, n_samples, hop, n_mels, frames, min_db, ref_db);
+    VIAI_LAUNCH(kern, dim3(grid), dim3(Cfg::NT), Cfg::lds, st, wav, window, basis_t, band_lo, band_cnt, mask, mel, B, n_samples, hop, n_mels, frames, min_db, ref_db, rt);
     return viai_launch_status();
 }
 
@@ -699,6 +830,15 @@ StftRoute stft_route(int n_samples, int fft, int hop, int n_mels, bool wav_align
     return StftRoute::banded;
 }
 
+// Frames per output tile of the three fft = 1024 families: what the launches below instantiate and what viai_stft_mel_ragged_plan cuts a row by.
+constexpr int RG_TF_R512 = 32, RG_TF_WAVE = 32, RG_TF_BANDED = SB_F;
+constexpr int RG_MAX_LEN = 0x1fffffff;                       // ragged rows: a row's byte length is a 32-bit buffer range
+inline int rag_tile(StftRoute r) { return r == StftRoute::r512 ? RG_TF_R512 : r == StftRoute::wave ? RG_TF_WAVE : RG_TF_BANDED; }
+inline int rag_frames(int len, int fft, int hop) {           // lws_num_frames (utils/audio.py:90-98), with Python's floor division
+    const int a = len + (fft - hop) * 2 - fft;
+    return (a >= 0 ? a / hop : -((-a + hop - 1) / hop)) + (len % hop == 0 ? 1 : 2);
+}
+
 }  // namespace
 
 extern "C" int viai_stft_mel_route(int n_samples, int fft, int hop, int n_mels, int wav_aligned8, char* family, int cap) {
@@ -719,9 +859,9 @@ extern "C" int viai_stft_mel_banded(const float* wav, const float* window, const
     const auto st = (hipStream_t)stream;
     switch (stft_route(n_samples, fft, hop, n_mels, (reinterpret_cast<uintptr_t>(wav) & 7) == 0)) {
     case StftRoute::r512:
-        return launch_stft_r512<16, 32, 20, 10>(1, wav, window, basis_t, band_lo, band_cnt, mask, mel, B, n_samples, hop, n_mels, frames, min_level_db, ref_level_db, st);
+        return launch_stft_r512<16, RG_TF_R512, 20, 10>(1, wav, window, basis_t, band_lo, band_cnt, mask, mel, B, n_samples, hop, n_mels, frames, min_level_db, ref_level_db, st);
     case StftRoute::wave:
-        return launch_stft_wave<8, 32, 20, 2048, 1024>(1, wav, window, basis_t, band_lo, band_cnt, mask, mel, B, n_samples, hop, n_mels, frames, min_level_db, ref_level_db, st);
+        return launch_stft_wave<8, RG_TF_WAVE, 20, 2048, 1024>(1, wav, window, basis_t, band_lo, band_cnt, mask, mel, B, n_samples, hop, n_mels, frames, min_level_db, ref_level_db, st);
     case StftRoute::banded:
         break;
     default:
@@ -734,6 +874,83 @@ extern "C" int viai_stft_mel_banded(const float* wav, const float* window, const
     VIAI_LAUNCH(stft_mel_banded_kernel, grid, dim3(256), lds, st, wav, window, basis_t, band_lo, band_cnt, mask, mel, n_samples, hop, n_mels,
                 frames, min_level_db, ref_level_db);
     return viai_launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Ragged call: the host plan.  Frames per item = the output tile of the family's kernel (the launch instantiations below use the same constants), so a row is
+// cut exactly as a one-clip launch of its family cuts it.  No HIP call in here.
+extern "C" long viai_stft_mel_ragged_plan(const long long* row_off, const int* row_len, int n_rows, int fft, int hop, int n_mels, int base_aligned8,
+                                          int* row_frames, int* frame_off, int* row_family, int* items, long item_cap, int* family_items) {
+    if (row_off == nullptr || row_len == nullptr || n_rows < 1 || fft != SB_N) return -1;
+    long total_frames = 0, n_items[4] = {0, 0, 0, 0};
+    for (int r = 0; r < n_rows; ++r) {
+        if (row_len[r] < 1 || row_len[r] > RG_MAX_LEN || row_off[r] < 0) return -1;
+        // the row's first sample is 8-byte aligned when the base is and the offset is even, or neither
+        const bool al = ((row_off[r] & 1) == 0) == (base_aligned8 != 0);
+        const StftRoute rt = stft_route(row_len[r], fft, hop, n_mels, al);
+        if (rt != StftRoute::r512 && rt != StftRoute::wave && rt != StftRoute::banded) return -1;
+        const int fr = rag_frames(row_len[r], fft, hop), tf = rag_tile(rt);
+        total_frames += fr;
+        n_items[(int)rt] += (fr + tf - 1) / tf;
+    }
+    const long need = n_items[1] + n_items[2] + n_items[3];
+    if (total_frames > 0x7fffffffL || need > 0x3fffffffL) return -1;          // int32 frame columns; int32 indices into the (row, frame) pairs
+    long at[4] = {0, 0, n_items[1], n_items[1] + n_items[2]};
+    const bool fill = items != nullptr && item_cap >= need;
+    long fo = 0;
+    for (int r = 0; r < n_rows; ++r) {
+        const bool al = ((row_off[r] & 1) == 0) == (base_aligned8 != 0);
+        const StftRoute rt = stft_route(row_len[r], fft, hop, n_mels, al);
+        const int fr = rag_frames(row_len[r], fft, hop), tf = rag_tile(rt);
+        if (row_frames != nullptr) row_frames[r] = fr;
+        if (frame_off != nullptr) frame_off[r] = (int)fo;
+        if (row_family != nullptr) row_family[r] = (int)rt;
+        fo += fr;
+        if (fill)
+            for (int f0 = 0; f0 < fr; f0 += tf) {
+                long& k = at[(int)rt];
+                items[2 * k] = r;
+                items[2 * k + 1] = f0;
+                ++k;
+            }
+    }
+    if (frame_off != nullptr) frame_off[n_rows] = (int)fo;
+    if (family_items != nullptr)
+        for (int i = 0; i < 3; ++i) family_items[i] = (int)n_items[i + 1];
+    return fill ? 0 : need;
+}
+
+extern "C" int viai_stft_mel_ragged(const float* wav, const long long* row_off, const int* row_len, const int* row_frames, const int* frame_off, const int* items,
+                                    const int* family_items, int n_rows, const float* window, const float* basis_t, const int* band_lo, const int* band_cnt,
+                                    const float* mask, float* out, int fft, int hop, int n_mels, int time_major, float min_level_db, float ref_level_db,
+                                    void* stream) {
+    if (wav == nullptr || row_off == nullptr || row_len == nullptr || row_frames == nullptr || frame_off == nullptr || items == nullptr ||
+        family_items == nullptr || out == nullptr || window == nullptr || basis_t == nullptr || band_lo == nullptr || band_cnt == nullptr)
+        return (int)hipErrorInvalidValue;
+    if (n_rows < 1 || fft != SB_N || hop <= 0 || hop > fft || n_mels <= 0) return (int)hipErrorInvalidValue;
+    const int n5 = family_items[0], nw = family_items[1], nb = family_items[2];
+    if (n5 < 0 || nw < 0 || nb < 0 || (long)n5 + nw + nb < 1 || (long)n5 + nw + nb > 0x3fffffffL) return (int)hipErrorInvalidValue;
+    // a family is launched only on a shape its kernel takes (what stft_route asks of every row of that family, less the per-row conditions)
+    if ((n5 > 0 && (n_mels > R5_MMAX || hop % 8 != 0)) || (nw > 0 && (n_mels > 1024 || hop % 8 != 0))) return (int)hipErrorInvalidValue;
+    const auto st = (hipStream_t)stream;
+    RagTab rt{row_off, row_len, row_frames, frame_off, items, time_major != 0};
+    int err = 0;
+    if (n5 > 0)
+        err = launch_stft_r512<16, RG_TF_R512, 20, 10, true>(1, wav, window, basis_t, band_lo, band_cnt, mask, out, n5, 0, hop, n_mels, 0, min_level_db, ref_level_db, st, rt);
+    if (err == 0 && nw > 0) {
+        rt.items = items + 2 * (size_t)n5;
+        err = launch_stft_wave<8, RG_TF_WAVE, 20, 2048, 1024, true>(1, wav, window, basis_t, band_lo, band_cnt, mask, out, nw, 0, hop, n_mels, 0, min_level_db, ref_level_db, st, rt);
+    }
+    if (err == 0 && nb > 0) {
+        rt.items = items + 2 * ((size_t)n5 + nw);
+        constexpr int lds = (8 * SB_N + 768) * (int)sizeof(float2);
+        static bool attr_done = false;
+        if (!attr_done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stft_mel_banded_ragged_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr_done = true; }
+        VIAI_LAUNCH(stft_mel_banded_ragged_kernel, dim3(nb < 512 ? nb : 512), dim3(256), lds, st, wav, window, basis_t, band_lo, band_cnt, mask, out, nb, hop, n_mels,
+                    min_level_db, ref_level_db, rt);
+        err = viai_launch_status();
+    }
+    return err;
 }
 
 // basis_t: [fft/2+1][n_mels] (transposed mel basis)

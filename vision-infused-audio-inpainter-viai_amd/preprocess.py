@@ -190,11 +190,15 @@ class UtterancePreprocessor:
                                      max(b - a for _, a, b, _, _ in kept), 0 if amax is None else amax.data_ptr(), self.rescaling_max, self.mode,
                                      self.mu, fft, hop, tab[4 * nk:].data_ptr(), rows.data_ptr(), ro, tab[5 * nk:].data_ptr(), signal.data_ptr(), so,
                                      _stream()), "viai_utt_pack")
+        # the mels of all rows in one ragged call, written (N, num_mels); a front end without `ragged` is called once per row as before
+        mels = None
+        if hasattr(self.front, "ragged"):
+            mels = self.front.ragged(rows, [e - s for _, _, _, s, e in kept], row_off, time_major=True)
         out = []
-        for (c, _, _, s, e), r0, s0 in zip(kept, row_off, sig_off):
+        for i, ((c, _, _, s, e), r0, s0) in enumerate(zip(kept, row_off, sig_off)):
             T = e - s
             _, _, N, steps = signal_layout(T, fft, hop)
             row = rows[r0:r0 + T]
-            mel = self.front(row[None])[0, 0].t().contiguous()
+            mel = mels[i] if mels is not None else self.front(row[None])[0, 0].t().contiguous()
             out.append(Utterance(signal[s0:s0 + steps], mel, steps, s, e, c, row))
         return out
