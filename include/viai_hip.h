@@ -491,6 +491,28 @@ enum { VIAI_UTT_MULAW_QUANTIZE = 0, VIAI_UTT_MULAW = 1, VIAI_UTT_RAW = 2 };
 int viai_utt_pack(const float* wav, long n_samples, const int* chunk_off, const int* chunk_len, const int* bounds, int n_chunks, int max_len,
                   const float* amax, float rescaling_max, int mode, int mu, int fft, int hop, const int* row_off, float* rows, long rows_cap,
                   const int* sig_off, void* signal, long signal_cap, void* stream);
+/* WaveNet training batches (csrc/vocoder_batch.hip, additive to ABI v20): `collate_fn` of Data_loaders/data_loader_utils.py:209-319 behind its
+ * crop draw -- crop on the frame grid, zero padding to the batch's longest row, targets, class / one-hot / float inputs and the mel transposed,
+ * in ONE launch for the whole batch.  Row b is a pair of viai_utt_pack's making, read where it lies:
+ *   sig_ptr[b]  its signal, int32 classes (mode VIAI_UTT_MULAW_QUANTIZE) or floats (VIAI_UTT_MULAW, VIAI_UTT_RAW), 4-byte aligned
+ *   mel_ptr[b]  its mel, (N, D) fp32 row-major; mel_ptr == NULL (with c == NULL): no local conditioning
+ *   start[b], frames[b]   the crop: frames [start, start + frames) of the mel, samples [start hop, (start + frames) hop) of the signal.
+ *                         The four tables are arrays of B entries in DEVICE memory; frames[b] is clamped to [0, L_out], start[b] to >= 0.
+ * With t < T_out = L_out * hop, len = frames[b] * hop and s = the row's signal from sample start[b] * hop on:
+ *   mode 0:     y [B][T_out] int64 (the (B, T, 1) targets) = s[t], 0 for t >= len;  classes [B][T_out] int32, the same numbers (NULL: not
+ *               written);  x [B][K][T_out] fp32 (NULL: not written) = 1.0 where s[t] == k, else 0.0 -- a column at t >= len, or of a class
+ *               outside [0, K), is all zero.  No store address depends on a class.
+ *   modes 1, 2: y is a float buffer [B][T_out] = the bits of s[t], 0.0 for t >= len: the (B, 1, T) input and the (B, T, 1) target of the
+ *               reference hold the same numbers in the same order, so one buffer is both.  classes and x are not touched.
+ *   c [B][D][L_out] fp32 = mel[start[b] + f][d] at [b][d][f], 0.0 for f >= frames[b].
+ * Nothing is read past sample (start + frames) * hop resp. frame start + frames of a row, nothing is written outside the extents above.
+ * 16-byte loads for a row when hop % 4 == 0 and its first kept sample is 16-byte aligned, 16-byte stores when every output base is 16-byte
+ * aligned and T_out % 4 == 0; element by element otherwise, same results.
+ * Refused on the host before any HIP call (so also without a device): a NULL sig_ptr, start, frames or y; B < 1 or > 65535; hop < 1; an unknown
+ * mode; K < 2 in mode 0; K % 4 != 0 with x given; D < 1 with mel_ptr given; mel_ptr without c or c without mel_ptr; T_out < hop,
+ * T_out % hop != 0, L_out * hop != T_out, T_out > INT32_MAX; an output pointer that is not aligned to its element.                          */
+int viai_voc_collate(const void* const* sig_ptr, const float* const* mel_ptr, const int* start, const int* frames, int B, int hop, int D, int mode,
+                     int K, long T_out, int L_out, long long* y, int* classes, float* x, float* c, void* stream);
 
 /* Incremental synthesis as ONE persistent launch (ABI v16, csrc/wavenet_pipe.hip): a weight-stationary pipeline for the reference-size
  * network (24 layers, 512 residual / 512 gate / 256 skip channels, 80 conditioning channels, 30 outputs, no global conditioning).  Every

@@ -165,6 +165,7 @@ SIGNATURES = {
     "viai_mel_compose": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "viai_utt_trim_bounds": (_I, [_P, _L, _P, _P, _I, _P, _F, _I, _I, _I, _P, _P]),
     "viai_utt_pack": (_I, [_P, _L, _P, _P, _P, _I, _I, _P, _F, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _P]),
+    "viai_voc_collate": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _P, _P, _P, _P, _P]),
     "viai_wn_categorical_ok": (_I, [C.POINTER(WnSynth)]),
     "viai_mulaw_decode": (_I, [_P, _P, _L, _I, _P]),
     "viai_mulaw_quantize": (_I, [_P, _P, _L, _I, _P]),
