@@ -460,6 +460,39 @@ int viai_wav_align(const float* wav, const int* a0, const int* a1, float* out, i
  * real, fake (B, 1, F, T) contiguous, mask (B, T), c (B, F, T) (the layout wavenet.py:291-299 up-samples).  Any F, T >= 1.                     */
 int viai_mel_compose(const float* real, const float* fake, const float* mask, float* c, int B, int F, int T, void* stream);
 
+/* ---- inpainting quality metrics (csrc/metrics.hip; additive to ABI v20) ----
+ * The sums behind SNR / SI-SDR over a gap in samples, L1 / PSNR / log-spectral distance over mel frames, and SSIM of two mel images.  Inputs are
+ * fp32, every sum is fp64 and taken in a fixed order (thread, wave, block, then a second launch over the block partials in chunk order; no
+ * atomics), over chunks laid on each stream's own region: results are the same bits from run to run, and a stream's row does not depend on the
+ * batch it is in.  Each call is two launches and needs `ws`, viai_metrics_ws_doubles(kind, ...) doubles of device memory that it overwrites;
+ * nothing is allocated and nothing syncs.  out and ws are 8-byte aligned.  Bad arguments (null pointers that are required, the shape rules
+ * below) return hipErrorInvalidValue before any launch.
+ * `where` selects frames against mask (B, T) -- the memory of a (B, 1, 1, T) time mask, 1 = known, 0 = damaged:
+ *     0 every frame (mask may be NULL), 1 frames with mask == 0, 2 frames with mask != 0.                                                      */
+#define VIAI_METRIC_WAVE 0
+#define VIAI_METRIC_MEL_FRAMES 1
+#define VIAI_METRIC_MEL_SSIM 2
+/* doubles of workspace for one call: kind WAVE (B, n), MEL_FRAMES (B, F, T), MEL_SSIM (B, F, T, taps); arguments a kind does not use are ignored.
+ * Pure host arithmetic; 0 for arguments the call itself refuses.                                                                             */
+long viai_metrics_ws_doubles(int kind, int B, int n_or_F, int T, int taps);
+/* ref, est (B, n); g0, glen: B int32 in DEVICE memory, the gap [g0[b], g0[b] + glen[b]) in samples, clamped to [0, n) on the device (never read
+ * past); odd starts and lengths are legal.  out (B, 5) = {count, sum ref^2, sum est^2, sum (ref - est)^2, sum ref est} over the gap; glen <= 0
+ * gives a row of zeros.  Chunk k of a gap is [g0 + 2048 k, g0 + 2048 (k + 1)).  Refuses B < 1, n < 1.                                        */
+int viai_wave_gap_stats(const float* ref, const float* est, const int* g0, const int* glen, double* out, double* ws, int B, int n, void* stream);
+/* ref, est (B, 1, F, T) contiguous, d = est - ref.  out (B, 4) = {frames counted, sum |d|, sum d^2, sum_t sqrt(mean_f (db_range d)^2)} over the
+ * selected frames; db_range = -min_level_db (100): the normalised mel is affine in dB, so the last entry is the log-spectral distance in dB,
+ * summed over frames, with no logarithm taken.  Refuses B, F, T < 1, where outside 0 .. 2, mask == NULL with where != 0.                     */
+int viai_mel_frame_stats(const float* ref, const float* est, const float* mask, double* out, double* ws, int B, int F, int T, int where,
+                         double db_range, void* stream);
+/* SSIM (Wang et al. 2004) with the separable window win (x) win -- `taps` doubles in HOST memory, read before the call returns, expected to sum
+ * to 1 -- and population moments: mu = E[.], var_x = E[x^2] - mu_x^2, cov = E[xy] - mu_x mu_y,
+ *     ssim = ((2 mu_x mu_y + c1) (2 cov + c2)) / ((mu_x^2 + mu_y^2 + c1) (var_x + var_y + c2)).
+ * "Valid" mode: the (F - taps + 1) x (T - taps + 1) positions whose window lies inside the image; position (f, t) reads rows f .. f + taps - 1,
+ * frames t .. t + taps - 1 and belongs to its CENTRE frame t + taps / 2, which `where` tests.  out (B, 2) = {positions counted, sum of ssim}.
+ * Refuses even taps, taps > 31, F < taps, T < taps.                                                                                           */
+int viai_mel_ssim(const float* ref, const float* est, const float* mask, const double* win, double* out, double* ws, int B, int F, int T,
+                  int taps, int where, double c1, double c2, void* stream);
+
 /* ---- vocoder data preparation: waveform -> (signal, aligned row) per chunk (additive to ABI v20, csrc/preprocess.hip) ----
  * `_process_utterance` of utils/librivox.py:44-117 behind the file decode.  A file wav (n_samples floats) is cut into n_chunks chunks
  * [chunk_off[c], chunk_off[c] + chunk_len[c]) -- int32 arrays in DEVICE memory; the part of a chunk outside the file is ignored.  Each call is one

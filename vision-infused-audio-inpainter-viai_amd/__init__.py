@@ -10,6 +10,7 @@ name; the top-level `viai_amd/` shim maps the import name onto it).
   ddp       one-process-per-GPU gradient all-reduce over RCCL
   synth     closed-form synthetic MUSICES-shaped inputs
   inpaint   AudioInpainter: waveform in, waveform out (mel front end -> generator -> WaveNet vocoder); gap_frames
+  metrics   how good an inpainted clip is: gap SNR / SI-SDR, mel L1 / PSNR / log-spectral distance / SSIM, inpainting_report
 """
 __version__ = "0.1.0"
 

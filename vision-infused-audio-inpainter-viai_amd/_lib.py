@@ -163,6 +163,10 @@ SIGNATURES = {
     "viai_gap_frame_mask": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "viai_wav_align": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "viai_mel_compose": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "viai_metrics_ws_doubles": (_L, [_I, _I, _I, _I, _I]),
+    "viai_wave_gap_stats": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "viai_mel_frame_stats": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P]),
+    "viai_mel_ssim": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _P]),
     "viai_utt_trim_bounds": (_I, [_P, _L, _P, _P, _I, _P, _F, _I, _I, _I, _P, _P]),
     "viai_utt_pack": (_I, [_P, _L, _P, _P, _P, _I, _I, _P, _F, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _P]),
     "viai_voc_collate": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _P, _P, _P, _P, _P]),
