@@ -493,6 +493,38 @@ int viai_mel_frame_stats(const float* ref, const float* est, const float* mask, 
 int viai_mel_ssim(const float* ref, const float* est, const float* mask, const double* win, double* out, double* ws, int B, int F, int T,
                   int taps, int where, double c1, double c2, void* stream);
 
+/* ---- polyphase resampler: a clip at any sample rate (csrc/wav_resample.hip; additive to ABI v20) ----
+ * sr_in -> sr_out with g = gcd, L = sr_out / g, M = sr_in / g, s = min(1, L / M), c = rolloff s, W = zeros / s, H = ceil(W), T = 2 H + 1.
+ * Output k sits at input time k M / L; with i0 = floor(k M / L) and r = (k M) mod L
+ *     y[k] = sum_{j = 0 .. T - 1} x[i0 - H + j] h_r[j],     h_r[j] = c sinc(c t) kaiser(t / W),     t = r / L - (j - H),
+ * sinc(v) = sin(pi v) / (pi v), kaiser(u) = I0(beta sqrt(1 - u^2)) / I0(beta) for |u| < 1 and 0 otherwise, x zero outside [0, length).
+ * TABLE LAYOUT: period order, tap-major.  Row q = k mod L of the table holds phase r = (q M) mod L, first[q] = floor(q M / L), and
+ * tap j of row q is taps[j * L + q]: output k = p L + q reads x[p M + first[q] - H + j] against taps[j * L + q], so consecutive outputs of one
+ * period read consecutive words.  L * T floats and L ints.
+ * Plans whose table L * T exceeds VIAI_WAV_RESAMPLE_MAX_TABLE words are refused, by the plan and by the launch.                              */
+#define VIAI_WAV_RESAMPLE_MAX_TABLE 4194304
+/* pure arithmetic.  Refuses (hipErrorInvalidValue) rates below 1, zeros < 1, null pointers and a table over the cap.                          */
+int viai_wav_resample_geom(int sr_in, int sr_out, int zeros, int* L, int* M, int* H, int* T);
+/* the table in HOST memory: taps L * T floats, first L ints, computed in fp64 (I0 by its power series) and rounded once to fp32.  Refuses what
+ * the plan refuses, rolloff outside (0, 1] and beta outside [0, 700).                                                                         */
+int viai_wav_resample_taps(int sr_in, int sr_out, int zeros, double rolloff, double beta, float* taps, int* first);
+/* ceil(n L / M), the outputs of n input samples; 0 for n < 0 or L, M < 1                                                                      */
+long viai_wav_resample_out_len(long n, int L, int M);
+/* the resampler's counterpart of gap_frames: the outputs k in [0, m) whose filter support [i0 - H, i0 + H] meets the input gap [g0, g1):
+ * k0 = max(0, ceil((g0 - H) L / M)), k1 = min(m, ceil((g1 + H) L / M)); an empty gap (g1 <= g0), or one no output meets, gives (0, 0).
+ * Pure host arithmetic in 64 bits.                                                                                                            */
+int viai_gap_at_rate(long g0, long g1, int L, int M, int H, long m, long* k0, long* k1);
+/* x (B, x_stride) fp32; lengths (B,) int32 in DEVICE memory or NULL (every row x_stride long), clamped to [0, x_stride]: samples at and beyond a
+ * row's length read as zero.  taps, first: the table above in DEVICE memory.  y (B, y_stride) fp32.  o0, o1 (B,) int32 in DEVICE memory or NULL:
+ * the call writes the outputs k in [o0[b], o1[b]) intersected with [0, m) (NULL: [0, m)) and leaves every other element of y untouched.
+ * One launch for the batch, nothing allocated, nothing syncs.  Each output is the fp32 chain acc = fma(x, h, acc), j = 0 .. T - 1, from +0:
+ * y[b][k] has the same bits for a row alone, in any batch and under any window.  Outputs past ceil(length L / M) follow the same formula: they
+ * decay over the filter's support and are exact zeros from ceil((length + H) L / M) on.
+ * Refuses before any launch: x, taps, first or y NULL; B, m, L, M or T < 1; T != 2 H + 1; x_stride < 1; y_stride < m; a table over the cap;
+ * a plan whose smallest tile (64 outputs and 2 H + 3 samples of halo) does not fit 64 KiB of LDS.                                            */
+int viai_wav_resample(const float* x, const int* lengths, const float* taps, const int* first, float* y, const int* o0, const int* o1, int B,
+                      long x_stride, long y_stride, int m, int L, int M, int H, int T, void* stream);
+
 /* ---- vocoder data preparation: waveform -> (signal, aligned row) per chunk (additive to ABI v20, csrc/preprocess.hip) ----
  * `_process_utterance` of utils/librivox.py:44-117 behind the file decode.  A file wav (n_samples floats) is cut into n_chunks chunks
  * [chunk_off[c], chunk_off[c] + chunk_len[c]) -- int32 arrays in DEVICE memory; the part of a chunk outside the file is ignored.  Each call is one

@@ -11,6 +11,7 @@ name; the top-level `viai_amd/` shim maps the import name onto it).
   synth     closed-form synthetic MUSICES-shaped inputs
   inpaint   AudioInpainter: waveform in, waveform out (mel front end -> generator -> WaveNet vocoder); gap_frames
   metrics   how good an inpainted clip is: gap SNR / SI-SDR, mel L1 / PSNR / log-spectral distance / SSIM, inpainting_report
+  wav_resample  clips at any sample rate: Resampler (polyphase, HIP), gap_at_rate, inpaint_at_rate
 """
 __version__ = "0.1.0"
 
