@@ -525,6 +525,37 @@ int viai_gap_at_rate(long g0, long g1, int L, int M, int H, long m, long* k0, lo
 int viai_wav_resample(const float* x, const int* lengths, const float* taps, const int* first, float* y, const int* o0, const int* o1, int B,
                       long x_stride, long y_stride, int m, int L, int M, int H, int T, void* stream);
 
+/* ---- gap detection: where a waveform is damaged (csrc/gap_detect.hip; additive to ABI v20) ----
+ * A sample is DAMAGED when it is not finite, or |x| <= threshold, or (clip > 0 and |x| >= clip).  threshold = 0 means exact zeros, -0.0 included;
+ * clip = 0 switches the clipping test off.  For row b, len = clamp(lengths[b], 0, n), or n when lengths is NULL:
+ *   1  a RAW RUN is a maximal interval [s, e) of damaged samples inside [0, len); samples at and beyond len do not exist, they neither start nor
+ *      extend a run;
+ *   2  a raw run is KEPT when e - s >= min_len;
+ *   3  kept runs are taken in order of position, and a kept run JOINS the one before it when s - e_prev <= merge_within; the joined run is
+ *      [s_first, e_last).  The distance is between kept runs: a dropped short run between them counts as ordinary samples.  With
+ *      merge_within = 0 nothing joins (two maximal runs are at least one sample apart);
+ *   4  count[b] is the number of runs after 3 and may exceed K; start[b][k], length[b][k] hold the first K of them in position order, and the
+ *      entries k >= min(count[b], K) are written as 0.
+ * count (B,), start and length (B, K) are int32.  The results are exact, the same from run to run, and the same for a row alone or in any batch:
+ * the order comes from an exclusive sum over the tiles of a row, no atomic is involved.
+ * One block owns VIAI_GAP_DETECT_TILE samples of one row (tile t of a row is [t TILE, (t + 1) TILE), counted from the row's first sample).      */
+#define VIAI_GAP_DETECT_TILE 4096
+/* bytes of workspace for one call: the 1-bit-per-sample mask and a small table per tile.  Pure host arithmetic; 0 for arguments the call itself
+ * refuses (B, n or K < 1, n >= 2^31, more than 2^31 - 1 tiles in the batch).                                                                   */
+long viai_gap_detect_ws_bytes(int B, long n, int K);
+/* wav (B, stride) fp32, row b at wav + b stride, in DEVICE memory; lengths (B,) int32 in DEVICE memory or NULL; count, start, length in DEVICE
+ * memory; ws: viai_gap_detect_ws_bytes(B, n, K) bytes of device memory, 8-byte aligned, overwritten.  THREE launches for the whole batch (mask and
+ * per-tile summary; one block per row over the summaries; the runs written in place); nothing is allocated and nothing syncs.  Rows are read with
+ * 16-byte loads where wav + b stride is 16-byte aligned and with 4-byte loads otherwise; no sample at or beyond len is read.
+ * Refuses with hipErrorInvalidValue before any launch: wav, count, start, length or ws NULL; B, n or K < 1; n >= 2^31; stride < n; min_len < 1;
+ * merge_within < 0; a negative or NaN threshold; a negative or NaN clip; wav not 4-byte or ws not 8-byte aligned; more than 2^31 - 1 tiles.   */
+int viai_gap_detect(const float* wav, const int* lengths, long stride, int B, long n, float threshold, float clip, int min_len, int merge_within,
+                    int K, int* count, int* start, int* length, void* ws, void* stream);
+/* the same rule stated sample by sample in plain C++, every pointer in HOST memory: the statement the kernels are tested against, and the call for
+ * a user without a GPU.  Same refusals (ws and the alignment rules apart).                                                                    */
+int viai_gap_detect_host(const float* wav, const int* lengths, long stride, int B, long n, float threshold, float clip, int min_len,
+                         int merge_within, int K, int* count, int* start, int* length);
+
 /* ---- vocoder data preparation: waveform -> (signal, aligned row) per chunk (additive to ABI v20, csrc/preprocess.hip) ----
  * `_process_utterance` of utils/librivox.py:44-117 behind the file decode.  A file wav (n_samples floats) is cut into n_chunks chunks
  * [chunk_off[c], chunk_off[c] + chunk_len[c]) -- int32 arrays in DEVICE memory; the part of a chunk outside the file is ignored.  Each call is one

@@ -12,6 +12,7 @@ name; the top-level `viai_amd/` shim maps the import name onto it).
   inpaint   AudioInpainter: waveform in, waveform out (mel front end -> generator -> WaveNet vocoder); gap_frames
   metrics   how good an inpainted clip is: gap SNR / SI-SDR, mel L1 / PSNR / log-spectral distance / SSIM, inpainting_report
   wav_resample  clips at any sample rate: Resampler (polyphase, HIP), gap_at_rate, inpaint_at_rate
+  gap_detect    where a clip is damaged: find_gaps (dropouts, clipping, non-finite samples; HIP), find_gaps_host, repair
 """
 __version__ = "0.1.0"
 

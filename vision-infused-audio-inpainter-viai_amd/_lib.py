@@ -172,6 +172,9 @@ SIGNATURES = {
     "viai_wav_resample_out_len": (_L, [_L, _I, _I]),
     "viai_gap_at_rate": (_I, [_L, _L, _I, _I, _I, _L, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "viai_wav_resample": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _I, _I, _I, _I, _I, _P]),
+    "viai_gap_detect_ws_bytes": (_L, [_I, _L, _I]),
+    "viai_gap_detect": (_I, [_P, _P, _L, _I, _L, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "viai_gap_detect_host": (_I, [_P, _P, _L, _I, _L, _F, _F, _I, _I, _I, _P, _P, _P]),
     "viai_utt_trim_bounds": (_I, [_P, _L, _P, _P, _I, _P, _F, _I, _I, _I, _P, _P]),
     "viai_utt_pack": (_I, [_P, _L, _P, _P, _P, _I, _I, _P, _F, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _P]),
     "viai_voc_collate": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _P, _P, _P, _P, _P]),
