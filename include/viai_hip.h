@@ -556,6 +556,82 @@ int viai_gap_detect(const float* wav, const int* lengths, long stride, int B, lo
 int viai_gap_detect_host(const float* wav, const int* lengths, long stride, int B, long n, float threshold, float clip, int min_len,
                          int merge_within, int K, int* count, int* start, int* length);
 
+/* ---- video front end: motion crop, square pad, resize (csrc/video_prep.hip; additive to ABI v20) ----
+ * Raw uint8 frames and flow maps of any H x W in, the blocks the generator's visual branch consumes out: `find_cluster`, `crop_image` and
+ * `padding_square` of Data_loaders/Image_preprocess.py:168-229,256-268 and the resize / flip / normalise / crop of
+ * Data_loaders/audio_loader.py:185-245.  Everything is integer arithmetic up to the last divide, so every result is exact.
+ *
+ * MOTION BOX.  flow_x, flow_y are (N, H, W) uint8.
+ *   1  S[y][x] = sum over the N frames of |fx - 127| + |fy - 127|, int32.  A pixel is in the MASK when S > 2 N (strict).
+ *   2  a column x is OCCUPIED when any pixel of it is in the mask; rows alike.
+ *   3  per axis, on the ascending list o[0 .. len) of occupied indices (`find_cluster`): min_idx = 0; repeat len - 1 times: if o[min_idx] + 5 is
+ *      not an occupied index, min_idx += 1.  max_idx = len - 1; repeat len - 1 times: if o[max_idx] - 5 is not an occupied index, max_idx -= 1.
+ *      min = o[min_idx], max = o[max_idx]; if min > max then max = min.  In closed form (what the kernel evaluates; the tests hold the two
+ *      against each other): min is the first occupied v whose v + 5 is occupied, or the last occupied index when there is none; max is the
+ *      last occupied v whose v - 5 is occupied, or the first occupied index when there is none.
+ *   4  an empty mask gives min = max = 0 on both axes.
+ *   5  box = (w_min, w_max, h_min, h_max, ok), int32, ok = (w_max - w_min >= min_extent) && (h_max - h_min >= min_extent).  The reference uses
+ *      min_extent = 50 and deletes the clip when ok is 0.
+ * CROP.  Rows [h_min, h_max) x columns [w_min, w_max): the upper bounds are EXCLUSIVE, as in the reference.  Before any address is formed the box
+ * is clamped to the frame (w_min to [0, W], w_max to [w_min, W], rows alike).  When ok == 0, or the clamped crop is empty, the WHOLE FRAME is
+ * taken instead: a choice made here for inference (the reference has no such clip left); `ok` tells a caller that wants to drop the clip.
+ * SQUARE PAD (`padding_square`).  ch x cw is the crop, side = max(ch, cw), d = side - min(ch, cw): the shorter axis gets d / 2 (integer division)
+ * pixels of grey 127 in front and d - d / 2 behind, on every channel.  The pad is a coordinate test, it is never stored.
+ * RESIZE side x side -> R x R: OpenCV's INTER_LINEAR for 8-bit images stated as integer arithmetic; one table serves both axes.  For d in [0, R):
+ *   f = float32((d + 0.5) * (side / R) - 0.5), the quotient, the product and the difference in fp64, each rounded once (no fused multiply-add);
+ *   s = floor(f), a = f - s in fp32; if s < 0: s = 0, a = 0; if s >= side - 1: s = side - 1, a = 0;
+ *   c0 = rint((1 - a) * 2048), c1 = rint(a * 2048), fp32, round-half-even; the second tap is s' = min(s + 1, side - 1).
+ *   horizontal  h = p[s] * c0 + p[s'] * c1 in int32, with the table entry of the output column;
+ *   vertical    q = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2 with (b0, b1) the entry of the output row and h0, h1 the
+ *               horizontal results on source rows s and s'; q is stored as min(q, 255).
+ * OpenCV is not a dependency and is not available to the tests, so parity with cv2.resize is RESTATED here, not pinned by a test.  Pinned are:
+ * identity for side == R, constant images stay constant (255 included), and at most 1 grey level from fp64 bilinear (align_corners = False).
+ * The reference writes the cropped frames to JPEG and reads them back before it resizes; that lossy round trip is deliberately not reproduced.
+ * FINISH: exactly viai_frames_prep on the R x R image: flip left to right, rows [crop_x, +size) and columns [crop_y, +size), (q - 127) / 128.
+ *
+ * SOURCES.  src1 == NULL: src0 is (N, H, W, C) uint8, channels interleaved; bgr != 0 reverses the channel axis (output channel c reads source
+ * channel C - 1 - c: the reference's cvtColor).  src1 != NULL: C must be 2, src0 and src1 are (N, H, W) planes that give channels 0 and 1
+ * (flow_x, flow_y); bgr swaps them.  frame_stride is the distance between frames in bytes, >= H W C (H W for planes and for the motion box).
+ * frames_index: n int32 in DEVICE memory, the frames to resample in output order (repeats allowed), or NULL for frames 0 .. n - 1 (n <= N);
+ * an index outside [0, N) is clamped, never followed.                                                                                         */
+#define VIAI_MOTION_TILE_W 256 /* pixels of a row one wave owns in the motion pass: 16 lanes x 16 pixels */
+#define VIAI_MOTION_TILE_H 4   /* rows of a tile: 4 x 16 lanes = one wave                                 */
+/* bytes of workspace of viai_motion_box: one occupancy byte per column per tile row and per row per tile column.  0 for refused H, W.       */
+long viai_motion_box_ws_bytes(int H, int W);
+/* Two launches, no atomics, nothing allocated, nothing synced, no copy to the host.  1: one wave per 4 x 256 tile streams both stacks once
+ * (16-byte loads where a row's 16 pixels are 16-byte aligned and inside the row, byte loads otherwise), keeps the 16 int32 sums of a lane in
+ * registers over the frames and writes the tile's row and column flags with plain stores.  2: one block ORs the flags, applies rule 3 to both
+ * axes and writes box (5 int32, DEVICE memory).  ws: viai_motion_box_ws_bytes(H, W) bytes of device memory, overwritten.
+ * Refuses with hipErrorInvalidValue before any launch: a NULL pointer; N < 1 or N > 2^22; H or W < 1 or >= 2^15; frame_stride < H W;
+ * min_extent < 0.                                                                                                                             */
+int viai_motion_box(const unsigned char* flow_x, const unsigned char* flow_y, long frame_stride, int N, int H, int W, int min_extent, int* box,
+                    void* ws, void* stream);
+/* the two launches of viai_motion_box on their own (viai_motion_box is one after the other): the flags of every tile into ws, and the box from
+ * the flags in ws.  For a caller that times or reuses them; same refusals.                                                                    */
+int viai_motion_flags(const unsigned char* flow_x, const unsigned char* flow_y, long frame_stride, int N, int H, int W, void* ws, void* stream);
+int viai_motion_box_of_flags(const void* ws, int H, int W, int min_extent, int* box, void* stream);
+/* rules 1 - 5 pixel by pixel and rule 3 as the sequential walk, in plain C++, every pointer in HOST memory.  Same refusals.                 */
+int viai_motion_box_host(const unsigned char* flow_x, const unsigned char* flow_y, long frame_stride, int N, int H, int W, int min_extent,
+                         int* box);
+/* bytes of workspace of viai_video_resize_u8 / viai_video_prepare: the resolved crop and the R-entry coefficient table.  0 for a refused R.   */
+long viai_video_prep_ws_bytes(int R);
+/* crop + pad + resize of n frames -> out uint8 (n, R, R, C), DEVICE memory.  box: 5 int32 in DEVICE memory (viai_motion_box's, or the caller's).
+ * Two launches: one block resolves the crop from box and makes the table once (fp64 / fp32 as in the rule) in ws; the second resamples.
+ * Refuses before any launch: a NULL src0, box, out or ws; C outside 1..4; src1 with C != 2; N < 1 or > 2^22; n < 1; n > N without frames_index;
+ * H or W < 1 or >= 2^15; R < 1 or > 2^13; a frame_stride below one frame.                                                                    */
+int viai_video_resize_u8(const unsigned char* src0, const unsigned char* src1, long frame_stride, int N, int H, int W, int C, int bgr,
+                         const int* box, const int* frames_index, int n, int R, unsigned char* out, void* ws, void* stream);
+/* crop + pad + resize + flip + crop + normalise in ONE resampling launch (behind the same table launch) that computes only the size x size
+ * window: out fp32 (n, size, size, 4) NHWC4 with channels >= C zero, or with nchw != 0 (n, C, size, size).  Bit for bit
+ * viai_frames_prep(viai_video_resize_u8(...)).  Refuses what viai_video_resize_u8 refuses, and size < 1, size > R, crop_x or crop_y < 0,
+ * crop_x + size > R, crop_y + size > R.                                                                                                       */
+int viai_video_prepare(const unsigned char* src0, const unsigned char* src1, long frame_stride, int N, int H, int W, int C, int bgr,
+                       const int* box, const int* frames_index, int n, int R, int size, int crop_x, int crop_y, int flip, int nchw, float* out,
+                       void* ws, void* stream);
+/* viai_video_resize_u8 in plain C++, every pointer (box and frames_index too) in HOST memory; no workspace.  Same refusals.                   */
+int viai_video_resize_u8_host(const unsigned char* src0, const unsigned char* src1, long frame_stride, int N, int H, int W, int C, int bgr,
+                              const int* box, const int* frames_index, int n, int R, unsigned char* out);
+
 /* ---- vocoder data preparation: waveform -> (signal, aligned row) per chunk (additive to ABI v20, csrc/preprocess.hip) ----
  * `_process_utterance` of utils/librivox.py:44-117 behind the file decode.  A file wav (n_samples floats) is cut into n_chunks chunks
  * [chunk_off[c], chunk_off[c] + chunk_len[c]) -- int32 arrays in DEVICE memory; the part of a chunk outside the file is ignored.  Each call is one

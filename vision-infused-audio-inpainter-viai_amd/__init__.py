@@ -13,6 +13,7 @@ name; the top-level `viai_amd/` shim maps the import name onto it).
   metrics   how good an inpainted clip is: gap SNR / SI-SDR, mel L1 / PSNR / log-spectral distance / SSIM, inpainting_report
   wav_resample  clips at any sample rate: Resampler (polyphase, HIP), gap_at_rate, inpaint_at_rate
   gap_detect    where a clip is damaged: find_gaps (dropouts, clipping, non-finite samples; HIP), find_gaps_host, repair
+  video     raw frames and flow maps -> the visual branch's blocks: motion_box, resize_u8, prepare, VideoFrontEnd (HIP), motion_box_host
 """
 __version__ = "0.1.0"
 
@@ -22,4 +23,7 @@ def __getattr__(name):
     if name in ("AudioInpainter", "gap_frames"):
         from . import inpaint
         return getattr(inpaint, name)
+    if name == "VideoFrontEnd":
+        from . import video
+        return video.VideoFrontEnd
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

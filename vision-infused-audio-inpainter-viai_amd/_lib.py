@@ -175,6 +175,15 @@ SIGNATURES = {
     "viai_gap_detect_ws_bytes": (_L, [_I, _L, _I]),
     "viai_gap_detect": (_I, [_P, _P, _L, _I, _L, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P]),
     "viai_gap_detect_host": (_I, [_P, _P, _L, _I, _L, _F, _F, _I, _I, _I, _P, _P, _P]),
+    "viai_motion_box_ws_bytes": (_L, [_I, _I]),
+    "viai_motion_box": (_I, [_P, _P, _L, _I, _I, _I, _I, _P, _P, _P]),
+    "viai_motion_flags": (_I, [_P, _P, _L, _I, _I, _I, _P, _P]),
+    "viai_motion_box_of_flags": (_I, [_P, _I, _I, _I, _P, _P]),
+    "viai_motion_box_host": (_I, [_P, _P, _L, _I, _I, _I, _I, _P]),
+    "viai_video_prep_ws_bytes": (_L, [_I]),
+    "viai_video_resize_u8": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "viai_video_prepare": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "viai_video_resize_u8_host": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P]),
     "viai_utt_trim_bounds": (_I, [_P, _L, _P, _P, _I, _P, _F, _I, _I, _I, _P, _P]),
     "viai_utt_pack": (_I, [_P, _L, _P, _P, _P, _I, _I, _P, _F, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _P]),
     "viai_voc_collate": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _P, _P, _P, _P, _P]),

@@ -2,8 +2,9 @@
 
 Mirrors what `Data_loaders/audio_loader.py` does on the host with numpy: frame normalisation `(px - 127) / 128`,
 left-right flip and random crop (`:185-245`), and the per-clip mel / audio windows with the `(T, D) -> (D, T)`
-transpose of `collate_fn` (`:471-475,508,523`).  Image decoding and `cv2.resize` stay on the host (data pipeline,
-out of scope): the inputs here are uint8 frames already resized to `image_rescal_size`."""
+transpose of `collate_fn` (`:471-475,508,523`).  The inputs here are uint8 frames already cropped, squared and resized to
+`image_rescal_size`; raw frames of any size go through `viai_amd.video` (motion crop, square pad and the resize on the device, with
+this normalisation in the same launch).  Image decoding stays on the host."""
 import torch
 
 from . import _lib
