@@ -632,6 +632,79 @@ int viai_video_prepare(const unsigned char* src0, const unsigned char* src1, lon
 int viai_video_resize_u8_host(const unsigned char* src0, const unsigned char* src1, long frame_stride, int N, int H, int W, int C, int bgr,
                               const int* box, const int* frames_index, int n, int R, unsigned char* out);
 
+/* ---- optical flow: TV-L1 from raw frames to the 8-bit flow maps (csrc/optical_flow.hip; additive to ABI v20) ----
+ * The flow maps the video front end takes came with the reference's dataset as JPEG files; nothing in the reference computes them.  That they
+ * are TV-L1 flow in the `dense_flow` encoding is an INFERENCE from Data_loaders/Image_preprocess.py (8-bit maps with "no motion" near 127, and a
+ * motion threshold of 2 per frame, which is exactly what a still pixel, encoded as 128, contributes), not a record.  This is a statement of
+ * TV-L1 of its own, not OpenCV's: parity with cv2's DualTVL1 is not claimed.
+ *
+ * ARITHMETIC.  fp32 throughout; only + - * / and sqrt, each correctly rounded and rounded ONCE (no contraction into fused multiply-adds, no
+ * fast-math).  Sums written a + b + c are evaluated left to right.  The per-pixel functions exist once (csrc/viai_flow_rule.h) and both the
+ * kernels and viai_optical_flow_host call them, so host and device agree bit for bit.  A fixed iteration count, no epsilon stop: no reductions,
+ * no decisions on the host.
+ *
+ * 1 GREY.  g = (4899 R + 9617 G + 1868 B + 8192) >> 14 in int32, then to float (OpenCV's 8-bit BT.601, restated, not pinned).  C = 3 or 4
+ *   interleaved channels (a fourth is ignored); bgr != 0 swaps R and B.  C = 1: the byte itself.
+ * 2 PYRAMID.  Level 0 is the grey image, level k + 1 has ((h + 1) / 2, (w + 1) / 2) samples (integer division):
+ *   L[k+1][y][x] = the 5 x 5 binomial at (2 y, 2 x) of level k, indices clamped to the image (replicated border).  ROWS FIRST: on each of the rows
+ *   2 y - 2 .. 2 y + 2, r = 0.0625 a + 0.25 b + 0.375 c + 0.25 d + 0.0625 e over the columns 2 x - 2 .. 2 x + 2, the five products summed left
+ *   to right; THEN the same expression over the five row results, top to bottom.  The number of levels is the largest S <= scales for which the
+ *   coarsest level has both sides >= 16, and at least 1 (viai_optical_flow_levels).
+ * 3 PER LEVEL, coarse to fine.  At the coarsest level u = v = 0.  p11 = p12 = p21 = p22 = 0 at the start of every level; they persist across the
+ *   level's warps.  I1x[y][x] = 0.5 (I1[y][min(x + 1, w - 1)] - I1[y][max(x - 1, 0)]), I1y alike along y; I1 is frame t + 1.
+ *   BILINEAR(A, cx, cy) on an h x w plane: cx is clamped to [0, w - 1] with `!(cx >= 0) ? 0 : cx > w - 1 ? w - 1 : cx` (a NaN lands on 0) BEFORE
+ *   the floor; x0 = floor(cx), x1 = min(x0 + 1, w - 1), ax = cx - x0; y alike; the value is
+ *   (1 - ay) ((1 - ax) A[y0][x0] + ax A[y0][x1]) + ay ((1 - ax) A[y1][x0] + ax A[y1][x1]).  No address is ever formed from an unclamped value.
+ *   Going to a finer level: u_f[y][x] = 2 BILINEAR(u_c, (x + 0.5) / 2 - 0.5, (y + 0.5) / 2 - 0.5), v alike.
+ * 4 PER WARP.  I1w, I1wx, I1wy = BILINEAR of I1, I1x, I1y at (x + u, y + v).  grad = I1wx I1wx + I1wy I1wy.
+ *   rho_c = I1w - I1wx u - I1wy v - I0.
+ * 5 PER ITERATION, `iterations` times per warp, lt = lam theta, taut = tau / theta:
+ *   rho = rho_c + I1wx u + I1wy v.  d = lt I1wx when rho < -(lt grad); d = -(lt I1wx) when rho > lt grad; otherwise d = (-rho / grad) I1wx when
+ *   grad > 1e-10, and 0 when not.  e alike with I1wy.
+ *   u = (u + d) + theta (dx(p11) + dy(p12)), v = (v + e) + theta (dx(p21) + dy(p22)), with the backward differences
+ *   dx(p)[x] = p[0] in the first column, -p[w - 2] in the last, p[x] - p[x - 1] between, and 0 when w == 1; dy alike over rows.
+ *   Then, from the NEW u: ux = u[x + 1] - u[x], 0 in the last column; uy = u[y + 1] - u[y], 0 in the last row;
+ *   den = 1 + taut sqrt(ux ux + uy uy); p11 = (p11 + taut ux) / den, p12 = (p12 + taut uy) / den.  p21, p22 the same from v.
+ * 6 OUTPUT.  flow (N - 1, 2, H, W) fp32, pixels per frame at the input's resolution, map i = frame i -> frame i + 1, channel 0 = u (along x).
+ *   ENCODING q = f < -bound ? 0 : f > bound ? 255 : rint(255 (f + bound) / (2 bound)), round half to even, the sum, the product, 2 bound and the
+ *   quotient rounded once each; a NaN encodes as 0.  A still pixel is 127.5 -> 128.  pad_last != 0 writes the last map once more, so N frames
+ *   give N maps.
+ *
+ * THE ITERATION KERNEL runs k <= VIAI_FLOW_MAX_ITERS_PER_LAUNCH iterations per launch: a block owns a VIAI_FLOW_TILE_H x VIAI_FLOW_TILE_W tile,
+ * stages u, v and the four p of the tile plus a halo of k pixels (cut at the image) in LDS and recomputes the halo; halo pixels outside the image
+ * are neither computed nor read.  A recomputed value runs the same operations on the same inputs, so THE RESULT DOES NOT DEPEND ON
+ * iters_per_launch, nor on the remainder launch when it does not divide `iterations`.  Launches read one copy of the state and write the other.
+ * No atomics, no cooperative launch, no waiting between blocks, no host synchronisation, nothing allocated; pair = grid z in every launch.   */
+#define VIAI_FLOW_TILE_W 32
+#define VIAI_FLOW_TILE_H 32
+#define VIAI_FLOW_MAX_ITERS_PER_LAUNCH 8
+#define VIAI_FLOW_ITERS_PER_LAUNCH 8 /* the default of the Python wrapper (DESIGN.md 11.2o has the measurement behind it) */
+/* levels the pyramid of an H x W frame gets for `scales`; 0 for refused arguments.  Host arithmetic.                                          */
+int viai_optical_flow_levels(int H, int W, int scales);
+/* bytes of workspace for `pairs` pairs (pairs + 1 frames): the pyramids, two copies of the six evolving planes and the four constants of a
+ * warp, 4 bytes x ((pairs + 1) x pyramid + 16 pairs H W).  0 for refused arguments (pairs < 1 or > 65535).  Host arithmetic.                 */
+long viai_optical_flow_ws_bytes(int pairs, int H, int W, int scales);
+/* launches of one viai_optical_flow call: 1 (grey) + S - 1 (pyramid) + S warps (1 + ceil(iterations / iters_per_launch)) + S - 1 (up-sampling)
+ * + 1 (store); it does not depend on N.  0 for refused arguments.                                                                             */
+int viai_optical_flow_launches(int H, int W, int scales, int warps, int iterations, int iters_per_launch);
+/* frames (N, H, W, C) uint8 in DEVICE memory, frame f at frames + f frame_stride -> flow (N - 1, 2, H, W) fp32, DEVICE memory.  ws:
+ * viai_optical_flow_ws_bytes(N - 1, H, W, scales) bytes of device memory, 4-byte aligned, overwritten.
+ * Refuses with hipErrorInvalidValue before any launch: a NULL pointer; N < 2 or N - 1 > 65535; H or W < 1 or >= 2^15; C not 1, 3 or 4;
+ * frame_stride < H W C; scales, warps or iterations < 1; iters_per_launch outside 1 .. 8; tau, lam or theta non-positive or NaN.            */
+int viai_optical_flow(const unsigned char* frames, long frame_stride, int N, int H, int W, int C, int bgr, float tau, float lam, float theta,
+                      int scales, int warps, int iterations, int iters_per_launch, float* flow, void* ws, void* stream);
+/* the same rule in plain C++, every pointer in HOST memory, no workspace, no GPU.  Same refusals (iters_per_launch is checked and otherwise
+ * has no effect, as on the device).                                                                                                           */
+int viai_optical_flow_host(const unsigned char* frames, long frame_stride, int N, int H, int W, int C, int bgr, float tau, float lam, float theta,
+                           int scales, int warps, int iterations, int iters_per_launch, float* flow);
+/* flow (pairs, 2, H, W) fp32 -> flow_x, flow_y (pairs + (pad_last != 0), H, W) uint8, DEVICE memory, one launch.  Refuses before the launch: a
+ * NULL pointer; pairs < 1 or > 65534; H or W < 1 or >= 2^15; a non-positive or NaN bound.                                                    */
+int viai_flow_encode_u8(const float* flow, int pairs, int H, int W, float bound, int pad_last, unsigned char* flow_x, unsigned char* flow_y,
+                        void* stream);
+/* the same in plain C++ on HOST pointers.  Same refusals.                                                                                     */
+int viai_flow_encode_u8_host(const float* flow, int pairs, int H, int W, float bound, int pad_last, unsigned char* flow_x,
+                             unsigned char* flow_y);
+
 /* ---- vocoder data preparation: waveform -> (signal, aligned row) per chunk (additive to ABI v20, csrc/preprocess.hip) ----
  * `_process_utterance` of utils/librivox.py:44-117 behind the file decode.  A file wav (n_samples floats) is cut into n_chunks chunks
  * [chunk_off[c], chunk_off[c] + chunk_len[c]) -- int32 arrays in DEVICE memory; the part of a chunk outside the file is ignored.  Each call is one

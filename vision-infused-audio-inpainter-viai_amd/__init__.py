@@ -14,6 +14,7 @@ name; the top-level `viai_amd/` shim maps the import name onto it).
   wav_resample  clips at any sample rate: Resampler (polyphase, HIP), gap_at_rate, inpaint_at_rate
   gap_detect    where a clip is damaged: find_gaps (dropouts, clipping, non-finite samples; HIP), find_gaps_host, repair
   video     raw frames and flow maps -> the visual branch's blocks: motion_box, resize_u8, prepare, VideoFrontEnd (HIP), motion_box_host
+  optical_flow  raw frames -> TV-L1 flow -> the 8-bit flow maps `video` takes: tvl1, encode_u8, flow_u8 (HIP), tvl1_host, encode_u8_host
 """
 __version__ = "0.1.0"
 
@@ -26,4 +27,7 @@ def __getattr__(name):
     if name == "VideoFrontEnd":
         from . import video
         return video.VideoFrontEnd
+    if name in ("tvl1", "encode_u8", "flow_u8", "tvl1_host", "encode_u8_host"):
+        from . import optical_flow
+        return getattr(optical_flow, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

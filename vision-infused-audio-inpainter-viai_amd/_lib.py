@@ -184,6 +184,13 @@ SIGNATURES = {
     "viai_video_resize_u8": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
     "viai_video_prepare": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "viai_video_resize_u8_host": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P]),
+    "viai_optical_flow_levels": (_I, [_I, _I, _I]),
+    "viai_optical_flow_ws_bytes": (_L, [_I, _I, _I, _I]),
+    "viai_optical_flow_launches": (_I, [_I, _I, _I, _I, _I, _I]),
+    "viai_optical_flow": (_I, [_P, _L, _I, _I, _I, _I, _I, _F, _F, _F, _I, _I, _I, _I, _P, _P, _P]),
+    "viai_optical_flow_host": (_I, [_P, _L, _I, _I, _I, _I, _I, _F, _F, _F, _I, _I, _I, _I, _P]),
+    "viai_flow_encode_u8": (_I, [_P, _I, _I, _I, _F, _I, _P, _P, _P]),
+    "viai_flow_encode_u8_host": (_I, [_P, _I, _I, _I, _F, _I, _P, _P]),
     "viai_utt_trim_bounds": (_I, [_P, _L, _P, _P, _I, _P, _F, _I, _I, _I, _P, _P]),
     "viai_utt_pack": (_I, [_P, _L, _P, _P, _P, _I, _I, _P, _F, _I, _I, _I, _I, _P, _P, _L, _P, _P, _L, _P]),
     "viai_voc_collate": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _P, _P, _P, _P, _P]),

@@ -224,6 +224,8 @@ class VideoFrontEnd:
     starts, use_image_num   clip l takes frames [starts[l], starts[l] + use_image_num), as `sample_data_new` does; host ints, validated.
                   None: all frames, L = 1.
     bgr           reverse the image's channel axis (the reference's cvtColor of a decoded BGR frame).
+    flow_x, flow_y   both None: computed from the image by `optical_flow.flow_u8(image, bgr=bgr, **flow_params)` (TV-L1, DESIGN.md 11.2o);
+                  exactly one of them is a ValueError.
 
     Four launches for the box and the tables, two resampling launches; no synchronisation, and the box is never read on the host."""
 
@@ -232,8 +234,18 @@ class VideoFrontEnd:
             raise ValueError("VideoFrontEnd: 1 <= image_size <= rescale_size")
         self.image_size, self.rescale_size, self.min_extent = int(image_size), int(rescale_size), int(min_extent)
 
-    def __call__(self, image, flow_x, flow_y, train=False, crop_x=0, crop_y=0, flip=False, starts=None, use_image_num=None, bgr=False):
+    def __call__(self, image, flow_x=None, flow_y=None, train=False, crop_x=0, crop_y=0, flip=False, starts=None, use_image_num=None, bgr=False,
+                 flow_params=None):
         _need_cuda(image, "VideoFrontEnd")
+        if (flow_x is None) != (flow_y is None):
+            raise ValueError("VideoFrontEnd: flow_x and flow_y come together, or neither (the flow is then computed from the image)")
+        if flow_x is None:
+            if image.dim() != 4 or image.size(3) != 3 or image.size(0) < 2:
+                raise ValueError("VideoFrontEnd: image is (N, H, W, 3) with N >= 2 when the flow is computed from it")
+            from .optical_flow import flow_u8
+            flow_x, flow_y = flow_u8(image, bgr=bgr, **(flow_params or {}))
+        elif flow_params is not None:
+            raise ValueError("VideoFrontEnd: flow_params belong to a call without flow_x and flow_y")
         if image.dim() != 4 or image.size(3) != 3 or flow_x.dim() != 3 or tuple(image.shape[:3]) != tuple(flow_x.shape):
             raise ValueError("VideoFrontEnd: image is (N, H, W, 3), flow_x and flow_y are (N, H, W)")
         N, s = image.size(0), self.image_size
