@@ -140,7 +140,7 @@ def test_synth_matches_oracle_generator():
 
 
 def test_capture_scratch_is_handed_to_the_capturing_model():
-    """ops.scratch_snapshot / scratch_take_new (model._capture): buffers created or grown after the snapshot leave the process-wide
+    """ops.scratch_snapshot / scratch_take_new (step_capture.CapturedStep): buffers created or grown after the snapshot leave the process-wide
     pool and go to the caller; older ones stay."""
     import torch
     from viai_amd import ops

@@ -32,7 +32,7 @@ def _worker(rank, world, port, out_dir):
     x = synth.uniform("ddp.x", (4, 6), -1, 1, ) if False else synth.mel_batch(4, 2, 3, "ddp.x", rank).reshape(4, 6)
     arena.zero_grad()
     net(x).pow(2).mean().backward()
-    # the product step exchanges the arena in BUCKETS: in-place sum-all-reduce of contiguous views (model._reduce_range)
+    # the product step exchanges the arena in BUCKETS: in-place sum-all-reduce of contiguous views (exchange.GradExchange._reduce)
     half = arena.size // 2
     ddp.all_reduce_sum_(arena.grad[half:])
     ddp.all_reduce_sum_(arena.grad[:half])

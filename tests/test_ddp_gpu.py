@@ -89,7 +89,7 @@ def _worker(rank, world, port, out_dir, norm):
 def test_two_process_product_step_exchanges_sums_and_keeps_replicas_identical(tmp_path, norm):
     """norm = "in": the decoder built with nn.InstanceNorm2d, whose layers run the conv kernel once per sample with the same weight --
     a gradient-ready hook armed for ONE backward invocation of the trigger layer would reduce a bucket the other samples are still
-    accumulating into; such models exchange whole arenas after the last weight gradient (model._plan_exchange)."""
+    accumulating into; such models exchange whole arenas after the last weight gradient (exchange.plan_buckets)."""
     import sys
     sys.path.insert(0, ROOT)
     port = _free_port()

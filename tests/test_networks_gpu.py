@@ -476,7 +476,7 @@ def _rccl_one_rank_body(port, marker):
     # eager: the exchange of a one-rank group is the identity and the three-stream step is deterministic -> bitwise equal
     for a, b in zip(outs[0], outs[1]):
         assert torch.equal(a, b)
-    # graph mode: the capture warm-up (two real steps) is rolled back (model._capture snapshots and restores parameters, Adam
+    # graph mode: the capture warm-up (two real steps) is rolled back (step_capture.CapturedStep snapshots and restores parameters, Adam
     # state and BatchNorm buffers), so three replayed steps land where three eager steps do
     for a, b in zip(outs[0], outs[2]):
         assert torch.isfinite(b).all()
@@ -486,7 +486,7 @@ def _rccl_one_rank_body(port, marker):
     # leave the way bench.py's ranks do: every collective of this process complete (device sync + barrier), then the communicator down BEFORE
     # the interpreter starts tearing the HIP context down.  Rounds 2 / 3 retried this child and left through os._exit because it "aborted now
     # and then in RCCL's set-up or teardown"; the abort (1 of 20 runs, tools/rccl_loop.sh) was the process-group watchdog thread querying an
-    # event while THIS thread was capturing the graph-mode model's step -- illegal under the default capture mode, fixed in model._capture
+    # event while THIS thread was capturing the graph-mode model's step -- illegal under the default capture mode, fixed in step_capture.CapturedStep
     # (capture_error_mode="thread_local" while a process group is up).  No retry, no hard exit.
     torch.cuda.synchronize()
     dist.barrier()
@@ -497,7 +497,7 @@ def _rccl_one_rank_body(port, marker):
 
 
 def test_gradient_exchange_over_rccl_is_wired_into_the_step(tmp_path):
-    """one-rank RCCL group on the GPU box: the two all-reduce points of the step (ddp.py, model._allreduce) run on the
+    """one-rank RCCL group on the GPU box: the two all-reduce points of the step (ddp.py, exchange.GradExchange) run on the
     real backend, between the side-stream joins and the Adam kernels, and leave a one-rank result unchanged.  (The
     world-size-2 semantics are covered on CPU by tests/test_ddp_gloo.py and on the GPU over gloo by tests/test_ddp_gpu.py.)
     Runs in a spawned process (one process group per interpreter) that initialises the communicator eagerly and takes it down in order; a
@@ -598,11 +598,16 @@ def test_three_stream_step_is_bitwise_the_single_stream_step(monkeypatch):
     s = O.cf_uniform("st.s", (2, 1, 80, 32), 0, 1).cuda()
     mask = O.make_mask(2, 32, "st.mask").cuda()
 
-    def run(wgrad, dreal):
-        monkeypatch.setenv("VIAI_WGRAD_STREAM", wgrad)
-        monkeypatch.setenv("VIAI_DREAL_STREAM", dreal)
+    def run(wgrad, dreal, clear=False):
+        for name, v in (("VIAI_WGRAD_STREAM", wgrad), ("VIAI_DREAL_STREAM", dreal)):
+            if clear:                                # the model's own choice of streams (eager, no visual branch: both)
+                monkeypatch.delenv(name, raising=False)
+            else:
+                monkeypatch.setenv(name, v)
         m = AudioModel(hp, device="cuda", use_graph=False)
         assert (m._wgrad_stream is not None) == (wgrad == "1") and (m._dreal_stream is not None) == (dreal == "1")
+        if clear:                                    # both side streams taken away before the first step, as bench.py does between steps
+            m._wgrad_stream = m._dreal_stream = None
         m.load_states(O.encoder_state(), O.decoder_state(), O.disc_state())
         m.set_inputs(s, mask)
         for i in range(3):
@@ -614,3 +619,6 @@ def test_three_stream_step_is_bitwise_the_single_stream_step(monkeypatch):
     for cfg in (("1", "0"), ("1", "1"), ("1", "1")):
         for a, b in zip(serial, run(*cfg)):
             assert torch.equal(a, b), cfg
+    # the side streams are plain attributes read at step time: a model built with them and stripped of them runs the serial step
+    for a, b in zip(serial, run("1", "1", clear=True)):
+        assert torch.equal(a, b)

@@ -14,14 +14,16 @@ reference credits (README.md:39) and is the build's declared spec:
 Memory layout: all parameters of an optimizer live in ONE flat fp32 arena (and
 their gradients / Adam moments in three more), so the optimizer is a single
 streaming kernel and data-parallel gradient exchange is one RCCL all-reduce per
-optimizer with no packing copies.  The whole step can be captured into HIP
-graphs (three segments, split at the two all-reduce points).
+optimizer with no packing copies (exchange.GradExchange).  The whole step can
+be captured into HIP graphs (three segments, split at the two all-reduce
+points: step_capture.CapturedStep).
 """
 from __future__ import annotations
 
-import ctypes
+import contextlib
 import math
 import os
+import weakref
 from collections import OrderedDict
 
 import torch
@@ -29,8 +31,10 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import check, load as lib
+from .exchange import GradExchange, plan_buckets
 from .networks import (ImageEmbedding2, MelDecoder, MelDecoderImage, MelDiscriminator, MelEncoder, MultiScaleDiscriminator,
                        to_nchw_view)
+from .step_capture import CapturedStep
 
 
 class StepConfig:
@@ -145,9 +149,6 @@ class FusedAdam:
         self.state.copy_(torch.tensor([step, self.lr, self.betas[0] ** step, self.betas[1] ** step], dtype=torch.float64))
 
 
-_PARKED_PLANS = []      # launch plans of models that were collected while a stream capture was in progress (see AudioModel.close)
-
-
 def make_time_mask(batch, frames, blank_length, generator=None, device="cpu"):
     """One full-height time gap [t0, t0+L) per clip (misc/pipeline2.png); t0 ~ U{T/8 .. 5T/8}."""
     lo, hi = frames // 8, (5 * frames) // 8
@@ -201,8 +202,7 @@ class AudioModel:
         # (and the static-buffer discipline) of graph mode, so it sets use_graph too.
         self.use_plan = bool(use_plan)
         self.use_graph = bool(use_graph) or self.use_plan
-        self._plans = None
-        self._graph_scratch = None
+        self._captured = CapturedStep(self.device, self.use_plan)
         self._consts = {}
         # weight gradients trail on a side stream (ops.WGRAD_STREAM) in eager mode: -3.5 % step time on one MI355X.  Inside
         # a captured hipGraph the fork/join edges cost more than the overlap returns (+2 %), so graph mode stays on one
@@ -217,11 +217,19 @@ class AudioModel:
         self._wgrad_stream = torch.cuda.Stream(device=self.device) if side else None
         dreal = os.environ.get("VIAI_DREAL_STREAM", "0" if one_stream else "1") != "0"
         self._dreal_stream = torch.cuda.Stream(device=self.device) if dreal else None
-        self._graphs = None
-        self._comm = None                  # data-parallel exchange stream (created on first use)
-        self._g_update_pending = False     # the G exchange + Adam(G) + re-pack of the previous step are still on _comm
         self._skip_exchange = False        # bench.py: measure the step without the collectives (comm_ms_exposed)
-        self._plan_exchange()
+
+        def has_instance_norm(*mods):
+            return any(isinstance(m, nn.InstanceNorm2d) for mod in mods if mod is not None for m in mod.modules())
+        plan = plan_buckets(self.arena_G, self.arena_D, self.num_D, self.use_video,
+                            has_instance_norm(self.Mel_Encoder, self.Mel_Decoder, self.VideoEncoder), has_instance_norm(self.netD))
+        # (a weak reference: the exchange reads this model's two switches at every call, and must not keep the model alive)
+        self.exchange = GradExchange(plan, weakref.proxy(self), self.pg, self.world, overlap=not self.use_graph, device=self.device)
+        # what one segment of the step hands to the next
+        self._fake = self._lc = self._loss_real = self._loss_fake = None
+        self._g_exchanged = False                  # the G gradients of this step went through the exchange stream
+        self._scalars_src = self._pred_fake_g = None
+        self._stepped_since_range_check = False    # a train step ran since get_loss_items last looked at the weight range
 
     # ------------------------------------------------------------------ setup
     def _build_optimizers(self):
@@ -239,95 +247,20 @@ class AudioModel:
         self.optimizer_G = FusedAdam(self.arena_G, c.lr, (c.beta1, c.beta2), c.eps, stateless)
         self.optimizer_D = FusedAdam(self.arena_D, c.lr, (c.beta1, c.beta2), c.eps)
 
-    def _plan_exchange(self):
-        """Gradient buckets of the data-parallel exchange: contiguous ranges of the flat gradient arenas in the order the
-        backward pass completes them.  An EARLY bucket (trigger parameter, lo, hi) goes to RCCL from a gradient-ready hook
-        (ops.GRAD_HOOKS) as soon as the layer owning the trigger has queued its gradients -- the rest of the backward chain
-        runs beside the collective; the LATE ranges follow after the last weight gradient.
-          D  (6.2 MB):  early [conv3.weight .. end) = conv3 + norm3 + conv4, 76 % of the bytes, ready after the second layer of
-                        the backward chain;  late [0 .. conv3.weight)
-          G (16.7 MB):  early [convblock3 .. end of G), then [G start .. convblock3) at deconv1_1;  late = E (+ the visual branch).
-        The G exchange, Adam(E,G) and the weight re-pack stay on the exchange stream and overlap the NEXT step's D(real) forward +
-        backward, which reads none of them (see _seg_forward_dstep)."""
-        aD, aG = self.arena_D, self.arena_G
-
-        def off(arena, name):
-            return arena.offsets[arena.names.index(name)]
-        self._early_D, self._late_D = [], [(0, aD.size)]
-        if self.num_D == 1:
-            o = off(aD, "D.conv3.weight")
-            self._early_D, self._late_D = [("D.conv3.weight", o, aD.size)], [(0, o)]
-        g_lo = off(aG, next(n for n in aG.names if n.startswith("G.")))
-        v_names = [n for n in aG.names if n.startswith("V.")]
-        g_hi = off(aG, v_names[0]) if v_names else aG.size
-        c3 = off(aG, "G.convblock3.conv3_0.weight")
-        head = "G.deconv1_1_1.weight" if self.use_video else "G.deconv1_1.weight"
-        self._early_G = [("G.convblock3.conv3_0.weight", c3, g_hi), (head, g_lo, c3)]
-        self._late_G = [(0, g_lo)] + ([(g_hi, aG.size)] if g_hi < aG.size else [])
-        # An InstanceNorm2d layer runs conv_bn_act once PER SAMPLE with the same weight (networks._instance_norm_layer): the trigger
-        # layer's backward is then invoked B times per pass and a hook armed for one invocation would hand the bucket to RCCL while the
-        # other samples are still accumulating into it.  Such models exchange each arena whole, after its last weight gradient.
-        def has_instance_norm(*mods):
-            return any(isinstance(m, nn.InstanceNorm2d) for mod in mods if mod is not None for m in mod.modules())
-        if has_instance_norm(self.netD):
-            self._early_D, self._late_D = [], [(0, aD.size)]
-        if has_instance_norm(self.Mel_Encoder, self.Mel_Decoder, self.VideoEncoder):
-            self._early_G, self._late_G = [], [(0, aG.size)]
+    # the gradient exchange (exchange.GradExchange), under the names tests and tools read
+    _early_G = property(lambda self: self.exchange.plan.early_G)
+    _late_G = property(lambda self: self.exchange.plan.late_G)
+    _g_update_pending = property(lambda self: self.exchange.g_update_pending)
 
     def _exchanging(self):
-        return (self.world > 1 or self._force_allreduce) and not self._skip_exchange
+        return self.exchange.exchanging()
 
     def _overlapped(self):
-        """bucketed exchange from inside the step (eager mode); graph mode exchanges between its captured segments instead"""
-        return self._exchanging() and not self.use_graph
-
-    def _comm_stream(self):
-        if self._comm is None:
-            self._comm = torch.cuda.Stream(device=self.device)
-        return self._comm
-
-    def _reduce_range(self, arena, lo, hi):
-        """sum-all-reduce of arena.grad[lo:hi] on the exchange stream, behind everything queued so far on the current stream
-        and on the weight-gradient stream (in-place on the arena: no packing copies)."""
-        from . import ddp
-        comm = self._comm_stream()
-        comm.wait_stream(torch.cuda.current_stream())
-        if ops.WGRAD_STREAM is not None:
-            comm.wait_stream(ops.WGRAD_STREAM)
-        with torch.cuda.stream(comm):
-            ddp.all_reduce_sum_(arena.grad[lo:hi], self.pg)
-
-    def _arm_hooks(self, arena, early, fire_at=1):
-        """register the early buckets of `arena` as gradient-ready hooks; `fire_at` = which invocation of the trigger layer's
-        backward completes its gradient (2 when both halves of loss_D are back-propagated in one pass)."""
-        ops.GRAD_HOOKS.clear()
-        if not self._overlapped():
-            return
-        for name, lo, hi in early:
-            p = arena.params[arena.names.index(name)]
-            state = {"n": fire_at}
-
-            def hook(state=state, lo=lo, hi=hi):
-                state["n"] -= 1
-                if state["n"] == 0:
-                    self._reduce_range(arena, lo, hi)
-            ops.GRAD_HOOKS[p.data_ptr()] = hook
-
-    def _finish_exchange(self, arena, late):
-        """after the backward pass: the late ranges, then hand the reduced gradients back to the main stream."""
-        ops.GRAD_HOOKS.clear()
-        if not self._overlapped():
-            return False
-        for lo, hi in late:
-            self._reduce_range(arena, lo, hi)
-        return True
+        return self.exchange.overlapped()
 
     def sync_pending_update(self):
-        """the main stream waits for the deferred G exchange + Adam(E,G) + re-pack of the previous step (no host sync).  Called at
-        the point of the next step that first touches E / G, and by everything that reads parameters between steps."""
-        if self._g_update_pending:
-            torch.cuda.current_stream().wait_stream(self._comm)
-            self._g_update_pending = False
+        """the main stream waits for the deferred G exchange + Adam(E,G) + re-pack of the previous step (GradExchange.sync_pending_update)"""
+        self.exchange.sync_pending_update()
 
     def load_states(self, E=None, G=None, D=None, V=None):
         """load state_dicts (e.g. the oracle's closed-form tables) without breaking the arenas."""
@@ -385,7 +318,7 @@ class AudioModel:
             flow = flow.to(self.device, dtype=torch.float32)
             if self.video is None or self.video.shape != video.shape:
                 self.video, self.flow = torch.empty_like(video), torch.empty_like(flow)
-                self._drop_graphs()
+                self._captured.drop()           # new input shape: the captured graphs are stale
             self.video.copy_(video)
             self.flow.copy_(flow)
         mel = data[2] if isinstance(data, (tuple, list)) else data
@@ -399,46 +332,23 @@ class AudioModel:
         if self.mel is None or self.mel.shape != mel.shape:
             self.mel = torch.empty_like(mel)
             self.mask = torch.empty_like(mask)
-            self._drop_graphs()
+            self._captured.drop()               # new input shape: the captured graphs are stale
         self.mel.copy_(mel)
         self.mask.copy_(mask)
 
-    def _drop_graphs(self):
-        """new input shape: the captured graphs are stale.  They may still be replaying (steps are asynchronous) and a hipGraphExec
-        must not be destroyed while in flight, so this is one of the few places that waits for the device."""
-        if self._graphs is not None:
-            torch.cuda.synchronize(self.device)
-            if self._plans is not None:
-                for p in self._plans:
-                    lib().viai_plan_destroy(p)
-                self._plans = None
-            self._graphs = None
-            self._graph_scratch = None
-            ops.drop_scratch()            # scratch buffers allocated while capturing live in the dead graphs' private memory pool
+    _captured = None        # __del__ of a half-built object: __init__ may have raised early
 
     def close(self):
-        """release what the launch plans hold (events, plan nodes).  Also runs from __del__, i.e. whenever the garbage collector gets
-        to a dropped model -- possibly in the middle of ANOTHER model's stream capture, where a device synchronisation would invalidate
-        that capture: plans are then parked and destroyed at the next close() outside a capture.  The process-wide scratch pool is
-        not touched from here (buffers a capture of THIS model allocated live in self._graph_scratch and go with the object)."""
-        plans, self._plans = (getattr(self, "_plans", None) or []), None      # __del__ of a half-built object: __init__ may have raised early
-        self._graphs = None
-        self._graph_scratch = None
-        if not plans and not _PARKED_PLANS:
-            return
-        try:
-            if torch.cuda.is_current_stream_capturing():
-                _PARKED_PLANS.extend(plans)
-                return
-            torch.cuda.synchronize(self.device)         # a plan's events / kernel nodes must not be destroyed while a replay is in flight
-            for p in plans + _PARKED_PLANS:
-                lib().viai_plan_destroy(p)
-            del _PARKED_PLANS[:]
-        except Exception:
-            pass                                        # interpreter shutdown: the driver is gone, nothing left to release
+        """release what the launch plans hold (CapturedStep.close); also runs from __del__"""
+        if self._captured is not None:
+            self._captured.close()
 
     def __del__(self):
         self.close()
+
+    def plan_info(self):
+        """per captured segment: nodes, kernels, kernels with a noted stream, copies, fills, streams, events, waits"""
+        return self._captured.plan_info()
 
     def _gan(self, pred, real):
         t = 1.0 if real else 0.0
@@ -493,6 +403,7 @@ class AudioModel:
         self.netD.requires_grad_(True)
         main = torch.cuda.current_stream()
         side = self._dreal_stream
+        ex = self.exchange
         # D on the real clip needs nothing from the generator: in eager mode its forward AND backward run on a second
         # stream next to the E+G forward (whose BatchNorm / streaming kernels leave the matrix pipes idle, and vice
         # versa).  loss_D = 0.5 * (loss_fake + loss_real) is back-propagated as two halves; each parameter gradient is
@@ -523,14 +434,14 @@ class AudioModel:
         if side is not None:
             main.wait_stream(side)                                     # real-branch gradients are in the arena
             loss_real.record_stream(main)                              # allocated on `side`, read below on main
-            self._arm_hooks(self.arena_D, self._early_D, 1)
+            ex.arm(self.arena_D, ex.plan.early_D, 1)
             loss_fake.backward(self._const(0.5))
         else:
-            self._arm_hooks(self.arena_D, self._early_D, 2)
+            ex.arm(self.arena_D, ex.plan.early_D, 2)
             torch.autograd.backward([loss_fake, loss_real], [self._const(0.5), self._const(0.5)])      # d(0.5 (fake + real)): the factor as seeds
         ops.join_wgrad()
-        if self._finish_exchange(self.arena_D, self._late_D):
-            main.wait_stream(self._comm)                               # Adam(D) and the G step need the reduced D gradients
+        if ex.finish(self.arena_D, ex.plan.late_D):
+            main.wait_stream(ex.stream)                                # Adam(D) and the G step need the reduced D gradients
         self._loss_real, self._loss_fake = loss_real.detach(), loss_fake.detach()      # -> losses[0], losses[4] at the end of the step (one launch)
 
     def _seg_dupdate_gstep(self, update=True):
@@ -539,6 +450,7 @@ class AudioModel:
         s = self.mel
         B, _, F, T = s.shape
         self.netD.requires_grad_(False)
+        ex = self.exchange
         pred = self.netD.forward_nhwc(self._fake)
         loss_gan = self._gan(pred, True)
         loss_l1 = ops.l1_mean(self._fake, s.view(B, F, T, 1))
@@ -548,13 +460,13 @@ class AudioModel:
         if self._lc is not None:
             roots.append(self._lc)
             seeds.append(self._const(self.cfg.lambda_contrast))
-        self._arm_hooks(self.arena_G, self._early_G, 1)
+        ex.arm(self.arena_G, ex.plan.early_G, 1)
         torch.autograd.backward(roots, seeds)
         ops.join_side_streams()                   # (the visual branch's flow network back-propagates on its own stream)
         if self._lc is not None:
             self.EmbeddingL2 = self._lc.detach()
         ops.join_wgrad()
-        self._g_exchanged = self._finish_exchange(self.arena_G, self._late_G)
+        self._g_exchanged = ex.finish(self.arena_G, ex.plan.late_G)
         self.netD.requires_grad_(True)
         # the six scalars get_loss_items reports, in one launch
         check(lib().viai_step_scalars(self._loss_real.data_ptr(), self._loss_fake.data_ptr(), loss_gan.data_ptr(), loss_l1.data_ptr(),
@@ -564,90 +476,15 @@ class AudioModel:
         self._pred_fake_g = pred
 
     def _seg_gupdate(self):
-        if getattr(self, "_g_exchanged", False) and not self.use_graph:
+        if self._g_exchanged and not self.use_graph:
             # Adam(E,G) + the batched weight re-pack stay on the exchange stream behind the collective; the main stream picks them
             # up at the first use of E / G in the next step (sync_pending_update)
-            with torch.cuda.stream(self._comm):
+            with torch.cuda.stream(self.exchange.stream):
                 self.optimizer_G.step(1.0 / self.world)
-            self._g_update_pending = True
+            self.exchange.g_update_pending = True
             self._g_exchanged = False
         else:
             self.optimizer_G.step(1.0 / self.world)
-
-    def _allreduce(self, arena):
-        """graph mode only: blocking whole-arena exchange between the captured segments."""
-        if self._exchanging():
-            from . import ddp
-            ddp.all_reduce_sum_(arena.grad, self.pg)
-
-    def _capture(self):
-        """three HIP graphs split at the two gradient all-reduce points."""
-        segs = (self._seg_forward_dstep, self._seg_dupdate_gstep, self._seg_gupdate)
-        # Warm-up on a side stream (allocator + lazy init).  The warm-up runs two REAL steps (both Adam updates, the
-        # BatchNorm running statistics) without any gradient exchange, so everything a step mutates is snapshotted first
-        # and put back afterwards: a (re-)capture -- first step, or a new input shape -- then leaves parameters, Adam
-        # moments / step counters and BatchNorm buffers exactly where they were, on every rank.
-        snap = self._mutable_state()
-        saved = [t.clone() for t in snap]
-        st = torch.cuda.Stream()
-        st.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(st):
-            for _ in range(2):
-                for f in segs:
-                    f()
-        torch.cuda.current_stream().wait_stream(st)
-        for t, v in zip(snap, saved):
-            t.copy_(v)
-        self.weights_changed()
-        graphs, plans = [], []
-        pool = None
-        before = ops.scratch_snapshot()
-        # torch hands out streams from a pool of 32 per device, round robin, and torch.cuda.graph's default capture stream is one pool
-        # stream made once per process: in a long-lived process it can be the very stream this model got as a side stream, and the
-        # captured branch would collapse into the origin.  Capture on a stream known to differ from both side streams.
-        taken = {st.cuda_stream for st in (self._wgrad_stream, self._dreal_stream) if st is not None}
-        cap = torch.cuda.Stream(device=self.device)
-        while cap.cuda_stream in taken:
-            cap = torch.cuda.Stream(device=self.device)
-        # With a process group up, ProcessGroupNCCL's watchdog THREAD polls its work events (hipEventQuery) whenever it likes; under the default
-        # capture mode ("global") that call is illegal from any thread while this one captures, the watchdog dies with
-        # hipErrorStreamCaptureUnsupported and takes the process with it -- the "RCCL abort now and then" of rounds 2 and 3 (1 of 20 runs of the
-        # one-rank test; it was never RCCL's set-up or teardown).  "thread_local" confines the check to the capturing thread.
-        dist_up = torch.distributed.is_available() and torch.distributed.is_initialized()
-        gkw = {"capture_error_mode": "thread_local"} if dist_up else {}
-        for f in segs:
-            if self.use_plan:
-                # the capture is a recorder: the hipGraph is kept (it owns the kernel-argument arrays) but never instantiated
-                g = torch.cuda.CUDAGraph(keep_graph=True)
-                check(lib().viai_plan_log_begin(), "viai_plan_log_begin")
-                try:
-                    with torch.cuda.graph(g, pool=pool, stream=cap, **gkw):
-                        origin = torch.cuda.current_stream().cuda_stream
-                        f()
-                finally:
-                    lib().viai_plan_log_end()
-                plan = ctypes.c_void_p()
-                check(lib().viai_plan_build(int(g.raw_cuda_graph()), origin, ctypes.byref(plan)), "viai_plan_build")
-                plans.append(plan)
-            else:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool, stream=cap, **gkw):
-                    f()
-            pool = g.pool()
-            graphs.append(g)
-        self._graphs = graphs
-        self._plans = plans if self.use_plan else None
-        # scratch buffers first requested inside the captures came from the graphs' private pool: they belong to this model now
-        self._graph_scratch = ops.scratch_take_new(before)
-
-    def plan_info(self):
-        """per captured segment: nodes, kernels, kernels with a noted stream, copies, fills, streams, events, waits"""
-        out = []
-        for p in self._plans or ():
-            v = (ctypes.c_int * 8)()
-            check(lib().viai_plan_info(p, v, 8), "viai_plan_info")
-            out.append(list(v))
-        return out
 
     def _mutable_state(self):
         """every device tensor a train step writes and the next step reads: parameter arenas, Adam moments and step
@@ -660,49 +497,43 @@ class AudioModel:
                 ts += [b for b in mod.buffers()]
         return ts
 
-    def optimize_parameters(self, global_step=0):
-        """one G+D train step (train_whole_sync.py:76)."""
-        prev, ops.DIRECT_GRAD = ops.DIRECT_GRAD, True      # gradients land in the arenas in place
+    @contextlib.contextmanager
+    def _step_scope(self):
+        """the ops module switches of a step: gradients land in the arenas in place (DIRECT_GRAD), weight gradients trail on this
+        model's side stream as it is NOW (bench.py reassigns _wgrad_stream between steps); put back, and the gradient-ready hooks
+        dropped, however the step ends"""
+        prev, ops.DIRECT_GRAD = ops.DIRECT_GRAD, True
         prev_s, ops.WGRAD_STREAM = ops.WGRAD_STREAM, self._wgrad_stream
         try:
-            self._optimize_parameters()
-            self._stepped_since_range_check = True
+            yield
         finally:
             ops.DIRECT_GRAD, ops.WGRAD_STREAM = prev, prev_s
+            ops.GRAD_HOOKS.clear()
 
-    def _optimize_parameters(self):
-        if self.use_graph:
-            if self._graphs is None:
-                self._capture()
-            if self.use_plan:
-                run = [lambda p=p: check(lib().viai_plan_replay(p, torch.cuda.current_stream().cuda_stream), "viai_plan_replay")
-                       for p in self._plans]
+    def optimize_parameters(self, global_step=0):
+        """one G+D train step (train_whole_sync.py:76)."""
+        with self._step_scope():
+            if self.use_graph:
+                ex = self.exchange
+                self._captured.run((self._seg_forward_dstep, self._seg_dupdate_gstep, self._seg_gupdate),
+                                   (lambda: ex.allreduce(self.arena_D), lambda: ex.allreduce(self.arena_G)),
+                                   state=self._mutable_state, restored=self.weights_changed,
+                                   avoid=(self._wgrad_stream, self._dreal_stream))
             else:
-                run = [g.replay for g in self._graphs]
-            run[0]()
-            self._allreduce(self.arena_D)
-            run[1]()
-            self._allreduce(self.arena_G)
-            run[2]()
-        else:
-            self._seg_forward_dstep()          # D exchange: early bucket from inside the backward, the rest at its end
-            self._seg_dupdate_gstep()          # G exchange: two early buckets + the encoder range
-            self._seg_gupdate()
+                self._seg_forward_dstep()          # D exchange: early bucket from inside the backward, the rest at its end
+                self._seg_dupdate_gstep()          # G exchange: two early buckets + the encoder range
+                self._seg_gupdate()
+            self._stepped_since_range_check = True
 
     def forward_backward_no_update(self):
         """the step WITHOUT the two Adam updates (parity target, see oracle.step_no_update).  In a process group the gradient
         arenas hold the all-reduced SUMS afterwards (the 1/N lives in the Adam kernel)."""
-        prev, ops.DIRECT_GRAD = ops.DIRECT_GRAD, True
-        prev_s, ops.WGRAD_STREAM = ops.WGRAD_STREAM, self._wgrad_stream
-        try:
+        with self._step_scope():
             self._seg_forward_dstep()
             self._seg_dupdate_gstep(update=False)
-            if getattr(self, "_g_exchanged", False):
-                torch.cuda.current_stream().wait_stream(self._comm)
+            if self._g_exchanged:
+                torch.cuda.current_stream().wait_stream(self.exchange.stream)
                 self._g_exchanged = False
-        finally:
-            ops.DIRECT_GRAD, ops.WGRAD_STREAM = prev, prev_s
-            ops.GRAD_HOOKS.clear()
 
     def test(self):
         """forward only (train_whole_sync.py:79-80,159-183: the caller sets `model.train = 0` and wraps in no_grad).
@@ -755,7 +586,7 @@ class AudioModel:
         losses there too, and ranks may hold unequal numbers of validation batches) and repeated reads on one rank do not communicate."""
         self.sync_pending_update()
         wr = self._weight_range_check()
-        stepped, self._stepped_since_range_check = getattr(self, "_stepped_since_range_check", False), False
+        stepped, self._stepped_since_range_check = self._stepped_since_range_check, False
         if self._exchanging() and stepped:
             # data-parallel runs: the weights are replicas, so every rank should see the same maxima -- but a rank whose replica has gone bad on its own (a
             # corrupted exchange, a NaN that only its clips produce) must not raise alone and leave the others waiting in the next collective: the flag is
