@@ -705,6 +705,48 @@ int viai_flow_encode_u8(const float* flow, int pairs, int H, int W, float bound,
 int viai_flow_encode_u8_host(const float* flow, int pairs, int H, int W, float bound, int pad_last, unsigned char* flow_x,
                              unsigned char* flow_y);
 
+/* ---- WAV in, WAV out: PCM decode, encode and in-place patching (csrc/wav_io.hip; additive to ABI v20) ----
+ * The data chunk of a WAV file is `frames` FRAMES of `channels` interleaved little-endian samples, 1 <= channels <= 8; a waveform is planar fp32,
+ * channel c at wav + c stride.  The per-sample arithmetic exists once, in csrc/viai_pcm_rule.h, for kernels and host mirrors: the same bits.
+ *   DECODE   U8 (b - 128) / 128; S16 v / 2^15; S24 three bytes sign-extended, v / 2^23; S32 (float)v rounded to nearest even, then 2^-31;
+ *            F32 the bits, non-finite values included; F64 the C cast to float.  mono: ((x0 + x1) + ...) + x_{C-1} in fp32 in channel order, then
+ *            one IEEE fp32 division by (float)C.
+ *   ENCODE   integer formats rint(x 2^(bits-1)), ties to even, clamped to the format's range in float before the conversion (x >= 1 is the
+ *            maximum, never a wrap); U8 rint(128 x) + 128 clamped to 0 .. 255; a non-finite x is 0 (128 for U8); F32 the bits; F64 the exact
+ *            widening.
+ *   NORMALISED ENCODE (S16 only; `save_wav` of utils/audio.py:19-21)  peak = max |x| over the finite samples of all channels; scale = 3276700.0f
+ *            when (double)peak <= 0.01, else the fp32 quotient 32767.0f / peak; the sample is (int16) trunc(fl32(x scale)); a non-finite sample
+ *            is 0 and does not enter the peak.
+ * One block owns VIAI_PCM_TILE frames: a multiple of 16, so a tile starts 16-byte aligned in the byte stream for every frame size (9-byte
+ * S24 x 3 frames included), and at most 64 KiB of bytes (8 channels of F64).                                                                   */
+enum { VIAI_PCM_U8 = 0, VIAI_PCM_S16 = 1, VIAI_PCM_S24 = 2, VIAI_PCM_S32 = 3, VIAI_PCM_F32 = 4, VIAI_PCM_F64 = 5 };
+#define VIAI_PCM_TILE 1024
+/* src: frames x channels samples, DEVICE memory, 16-byte aligned -> out (channels, frames) fp32, channel c at out + c out_stride, or (1, frames)
+ * when mono != 0.  ONE launch: a block brings its tile into LDS with 16-byte loads (the tail of the last tile byte by byte), lanes read their
+ * samples from LDS and write four frames of a plane with one 16-byte store where the address allows it.  frames = 0: nothing is launched.
+ * Every viai_pcm_* call refuses with hipErrorInvalidValue before any launch, and so also on a machine without a device: an unknown format;
+ * channels outside 1 .. 8; frames < 0 or more than 2^31 - 1 tiles; a stride < frames; a NULL pointer; src / dst not 16-byte or a waveform not
+ * 4-byte aligned (device calls only); normalize with a format other than S16.                                                                 */
+int viai_pcm_decode(const unsigned char* src, int fmt, int channels, long frames, int mono, float* out, long out_stride, void* stream);
+/* bytes of workspace of a normalised encode: one fp32 per tile.  Host arithmetic; 0 for frames < 0.                                           */
+long viai_pcm_ws_bytes(long frames);
+/* max |x| over the finite samples of every tile -> ws[tile] (fp32), one launch, one block per tile.  A maximum does not depend on order.      */
+int viai_pcm_peak(const float* wav, long stride, int channels, long frames, float* ws, void* stream);
+/* wav planar fp32 -> dst, frames x channels samples.  ONE launch without normalize (ws may be NULL); with it viai_pcm_peak runs first and every
+ * block of the encode launch reduces the partials itself: no atomic, no synchronisation, no host copy.  The transpose goes through LDS, dst
+ * is written with 16-byte stores (the tail byte by byte).                                                                                    */
+int viai_pcm_encode(const float* wav, long stride, int channels, long frames, int fmt, int normalize, unsigned char* dst, void* ws, void* stream);
+/* dst already holds the file's data bytes.  Encodes, plain rule, ONLY samples [start[c][k], start[c][k] + length[c][k]) of channel c, clamped to
+ * [0, frames), for k < min(count[c], K); count (channels,), start and length (channels, K) int32 in DEVICE memory, as viai_gap_detect leaves
+ * them.  Every store is as wide as one sample or narrower: no other byte of dst is read or written.  K < 1 is refused.                         */
+int viai_pcm_patch(const float* wav, long stride, int channels, long frames, int fmt, const int* count, const int* start, const int* length, int K,
+                   unsigned char* dst, void* stream);
+/* the same three in plain C++ from the same rule header, every pointer in HOST memory, no workspace, no alignment rule.  Same refusals.        */
+int viai_pcm_decode_host(const unsigned char* src, int fmt, int channels, long frames, int mono, float* out, long out_stride);
+int viai_pcm_encode_host(const float* wav, long stride, int channels, long frames, int fmt, int normalize, unsigned char* dst);
+int viai_pcm_patch_host(const float* wav, long stride, int channels, long frames, int fmt, const int* count, const int* start, const int* length,
+                        int K, unsigned char* dst);
+
 /* ---- vocoder data preparation: waveform -> (signal, aligned row) per chunk (additive to ABI v20, csrc/preprocess.hip) ----
  * `_process_utterance` of utils/librivox.py:44-117 behind the file decode.  A file wav (n_samples floats) is cut into n_chunks chunks
  * [chunk_off[c], chunk_off[c] + chunk_len[c]) -- int32 arrays in DEVICE memory; the part of a chunk outside the file is ignored.  Each call is one

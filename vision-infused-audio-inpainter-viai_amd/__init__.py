@@ -15,6 +15,7 @@ name; the top-level `viai_amd/` shim maps the import name onto it).
   gap_detect    where a clip is damaged: find_gaps (dropouts, clipping, non-finite samples; HIP), find_gaps_host, repair
   video     raw frames and flow maps -> the visual branch's blocks: motion_box, resize_u8, prepare, VideoFrontEnd (HIP), motion_box_host
   optical_flow  raw frames -> TV-L1 flow -> the 8-bit flow maps `video` takes: tvl1, encode_u8, flow_u8 (HIP), tvl1_host, encode_u8_host
+  wav_io    WAV in, WAV out: parse_wav, decode_pcm / encode_pcm / patch_pcm (HIP) and their _host mirrors, read_wav, write_wav, save_wav, repair_file
 """
 __version__ = "0.1.0"
 
@@ -30,4 +31,8 @@ def __getattr__(name):
     if name in ("tvl1", "encode_u8", "flow_u8", "tvl1_host", "encode_u8_host"):
         from . import optical_flow
         return getattr(optical_flow, name)
+    if name in ("WavInfo", "parse_wav", "decode_pcm", "decode_pcm_host", "encode_pcm", "encode_pcm_host", "patch_pcm", "patch_pcm_host",
+                "read_wav", "write_wav", "save_wav", "repair_file"):
+        from . import wav_io
+        return getattr(wav_io, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

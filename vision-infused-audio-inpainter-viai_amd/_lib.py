@@ -175,6 +175,14 @@ SIGNATURES = {
     "viai_gap_detect_ws_bytes": (_L, [_I, _L, _I]),
     "viai_gap_detect": (_I, [_P, _P, _L, _I, _L, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P]),
     "viai_gap_detect_host": (_I, [_P, _P, _L, _I, _L, _F, _F, _I, _I, _I, _P, _P, _P]),
+    "viai_pcm_decode": (_I, [_P, _I, _I, _L, _I, _P, _L, _P]),
+    "viai_pcm_ws_bytes": (_L, [_L]),
+    "viai_pcm_peak": (_I, [_P, _L, _I, _L, _P, _P]),
+    "viai_pcm_encode": (_I, [_P, _L, _I, _L, _I, _I, _P, _P, _P]),
+    "viai_pcm_patch": (_I, [_P, _L, _I, _L, _I, _P, _P, _P, _I, _P, _P]),
+    "viai_pcm_decode_host": (_I, [_P, _I, _I, _L, _I, _P, _L]),
+    "viai_pcm_encode_host": (_I, [_P, _L, _I, _L, _I, _I, _P]),
+    "viai_pcm_patch_host": (_I, [_P, _L, _I, _L, _I, _P, _P, _P, _I, _P]),
     "viai_motion_box_ws_bytes": (_L, [_I, _I]),
     "viai_motion_box": (_I, [_P, _P, _L, _I, _I, _I, _I, _P, _P, _P]),
     "viai_motion_flags": (_I, [_P, _P, _L, _I, _I, _I, _P, _P]),

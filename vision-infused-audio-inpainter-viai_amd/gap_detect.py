@@ -8,8 +8,7 @@ The rule (include/viai_hip.h states it in full): a sample is damaged when it is 
 Maximal runs of damaged samples inside a row's length are kept when they are at least `min_len` long; kept runs at most `merge_within` samples
 apart join into one.  The results are integers and exact: the same bits from run to run, and for a row alone or in any batch.
 
-A clip at another sample rate: run `find_gaps` on the clip itself and hand the gaps to `inpaint_at_rate`, or on the resampled clip.  Nothing is
-built here for that.
+A clip at another sample rate: `repair(..., sample_rate=...)` detects on the clip itself and runs every pass through `inpaint_at_rate`.
 """
 from __future__ import annotations
 
@@ -116,12 +115,15 @@ def find_gaps_host(wav, lengths=None, threshold=0.0, clip=0.0, min_len=64, merge
     return Gaps(count, start, length)
 
 
-def repair(inpainter, wav, gaps=None, uniforms=None, fade=0, **find_gaps_kwargs):
+def repair(inpainter, wav, gaps=None, uniforms=None, fade=0, sample_rate=None, **find_gaps_kwargs):
     """Detect the gaps of wav (B, n) and regenerate them with `inpainter` (an `AudioInpainter`).  Returns (waveform, Gaps).
 
     gaps       a `Gaps` from an earlier `find_gaps` (tensors or arrays); without it `find_gaps(wav, **find_gaps_kwargs)` runs.
     uniforms   a sequence with one entry per pass, each what `AudioInpainter.__call__` takes as `uniforms`; None: the sampler draws its own.
     fade       handed to every pass.
+    sample_rate  None (the default): wav is at the front end's rate and `inpainter` is called directly, exactly as before this argument existed.
+               A rate: pass k is `inpaint_at_rate(inpainter, wav, sample_rate, start[:, k], length[:, k], ...)`, which calls the inpainter
+               directly when the rate is the front end's; the overflow rule and the single copy of the lists to the host are the same.
 
     count, start and length come to the host ONCE (one synchronisation).  If any row has more gaps than the lists hold (count > K) a ValueError
     names the rows and nothing is repaired: an overflowing detection is never half repaired.  Then pass k = 0 .. max(count) - 1 calls
@@ -156,7 +158,12 @@ def repair(inpainter, wav, gaps=None, uniforms=None, fade=0, **find_gaps_kwargs)
         raise ValueError("repair: %d passes, uniforms for %d" % (passes, len(uniforms)))
     out = wav
     for k in range(passes):
-        out = inpainter(out, start[:, k].contiguous(), length[:, k].contiguous(), uniforms=None if uniforms is None else uniforms[k], fade=fade)
+        u = None if uniforms is None else uniforms[k]
+        if sample_rate is None:
+            out = inpainter(out, start[:, k].contiguous(), length[:, k].contiguous(), uniforms=u, fade=fade)
+        else:
+            from .wav_resample import inpaint_at_rate
+            out = inpaint_at_rate(inpainter, out, sample_rate, start[:, k].contiguous(), length[:, k].contiguous(), uniforms=u, fade=fade)
     if passes == 0:
         out = wav.float().clone()
     return out, gaps
