@@ -30,7 +30,7 @@ test_unpadded_output_layer_has_no_backward pins the refusal, and the padded form
 Bounds: tests/test_step_launches_gpu.py TOL (y, dx 2e-6; dw, db 3e-6 Frobenius-relative), unchanged, on every case; its adjointness bound 7.5e-10 of
 |y| |gy| from 2^21 output elements on, scaled by sqrt(2^21 / n) below (adj_bound: the figure of independent output errors goes like 1 / sqrt(n)).
 
-B. NON-CONV KERNELS (csrc/wavenet.hip), one row per launch branch:
+B. NON-CONV KERNELS (csrc/wavenet_ops.hip), one row per launch branch:
   weight_norm_fwd / _bwd     L = 1, L = 256 (one stride), 192 (< one stride), 576 and 1537 (loop, with remainder); accumulate 0 / 1   test_weight_norm
   glu_fwd / _bwd             yc NULL / set; H / 4 = 1, 8, 64; rows * H / 4 > 8192 * 256 (grid wraps)                                    test_glu, test_glu_grid_cap
   outer_fwd, outer_bwd_*     C / 4 = 16, 24 (256 / 24: 16 idle lanes), 512 (two group passes); one row, one block, four ragged blocks   test_outer

@@ -777,13 +777,6 @@ __global__ void act_bwd_out_kernel(const float* __restrict__ dz, const float* __
     }
 }
 
-inline int ew_blocks(long n) {
-    long b = (n + 255) / 256;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 }  // namespace
 
 extern "C" int viai_bn_finalize(const float* stat_part, int nblk, int rows_per_blk, long M, int C,
@@ -1020,13 +1013,13 @@ __global__ void add_act_bwd_out_kernel(const f32x4* __restrict__ dz, const f32x4
 }
 extern "C" int viai_add_act_bwd_from_output(const float* dz, const float* dz2, const float* z, float* dx, long n, int act, float slope, void* stream) {
     if (n % 4 != 0) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(add_act_bwd_out_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)dz, (const f32x4*)dz2, (const f32x4*)z, (f32x4*)dx,
+    VIAI_LAUNCH(add_act_bwd_out_kernel, dim3(viai_ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)dz, (const f32x4*)dz2, (const f32x4*)z, (f32x4*)dx,
                 n / 4, act, slope);
     return viai_launch_status();
 }
 
 extern "C" int viai_act_bwd_from_output(const float* dz, const float* z, float* dx, long n, int act, float slope, void* stream) {
-    VIAI_LAUNCH(act_bwd_out_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, dz, z, dx, n, act, slope);
+    VIAI_LAUNCH(act_bwd_out_kernel, dim3(viai_ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, dz, z, dx, n, act, slope);
     return viai_launch_status();
 }
 

@@ -25,13 +25,6 @@ inline ij_split ij_make(const void* out, long total) {
     return s;
 }
 
-inline int ij_blocks(long items) {
-    long b = (items + 255) / 256;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 // word index of scalar item k (0 <= k < head + tail)
 __device__ inline long ij_scalar(long k, int head, long nvec) { return k < head ? k : (long)head + 4 * nvec + (k - head); }
 
@@ -155,7 +148,7 @@ extern "C" int viai_gap_frame_mask(const int* a0, const int* a1, float* mask, in
     if (B < 1 || frames < 1 || fft < 1 || hop < 1 || a0 == nullptr || a1 == nullptr || mask == nullptr || !ij_word_aligned(mask))
         return (int)hipErrorInvalidValue;
     const ij_split s = ij_make(mask, (long)B * frames);
-    VIAI_LAUNCH(gap_frame_mask_kernel, dim3(ij_blocks(s.nvec + s.head + s.tail)), dim3(256), 0, (hipStream_t)stream, a0, a1, mask, frames, fft, hop, s.head,
+    VIAI_LAUNCH(gap_frame_mask_kernel, dim3(viai_ew_blocks(s.nvec + s.head + s.tail)), dim3(256), 0, (hipStream_t)stream, a0, a1, mask, frames, fft, hop, s.head,
                 s.nvec, s.tail);
     return viai_launch_status();
 }
@@ -166,7 +159,7 @@ extern "C" int viai_wav_align(const float* wav, const int* a0, const int* a1, fl
     const ij_split s = ij_make(out, (long)B * ((long)n + lpad));
     const unsigned* w = reinterpret_cast<const unsigned*>(wav);
     unsigned* o = reinterpret_cast<unsigned*>(out);
-    const dim3 grid(ij_blocks(s.nvec + s.head + s.tail));
+    const dim3 grid(viai_ew_blocks(s.nvec + s.head + s.tail));
     if (n % 4 == 0 && lpad % 4 == 0 && s.head == 0 && ij_vec_aligned(wav))
         VIAI_LAUNCH(wav_align_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, w, a0, a1, o, n, lpad, s.head, s.nvec, s.tail);
     else
@@ -183,7 +176,7 @@ extern "C" int viai_mel_compose(const float* real, const float* fake, const floa
     const unsigned* x = reinterpret_cast<const unsigned*>(real);
     const unsigned* y = reinterpret_cast<const unsigned*>(fake);
     unsigned* o = reinterpret_cast<unsigned*>(c);
-    const dim3 grid(ij_blocks(s.nvec + s.head + s.tail));
+    const dim3 grid(viai_ew_blocks(s.nvec + s.head + s.tail));
     if (ij_vec_aligned(x + s.head) && ij_vec_aligned(y + s.head))
         VIAI_LAUNCH(mel_compose_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, y, mask, o, FT, T, s.head, s.nvec, s.tail);
     else

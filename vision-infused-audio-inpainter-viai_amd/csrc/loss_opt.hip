@@ -91,6 +91,7 @@ __global__ void axpy_kernel(float a, const float* __restrict__ x, float* __restr
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] += a * x[i];
 }
 
+// not viai_ew_blocks: the cap here is 4096 blocks, and the losses' partial sums are laid out and added per block of that grid
 inline int ew_blocks(long n) {
     long b = (n + 255) / 256;
     if (b > 4096) b = 4096;

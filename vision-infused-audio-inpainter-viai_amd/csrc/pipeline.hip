@@ -9,13 +9,6 @@
 
 namespace {
 
-inline int ew_blocks_p(long n) {
-    long b = (n + 255) / 256;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 // frames: uint8 [n][S][S][C] (RGB or (flow_x, flow_y)), already resized to S x S.
 // out:    float [n][size][size][4] NHWC4 (channel C.. zero) -- the layout ResNet conv1 consumes -- with
 //         out[y][x] = (px(crop_x + y, flip ? S-1-(crop_y + x) : crop_y + x) - 127) / 128
@@ -115,7 +108,7 @@ __global__ __launch_bounds__(256) void l2_ranks_kernel(const float* __restrict__
 extern "C" int viai_frames_prep(const unsigned char* frames, float* out, long n, int S, int C, int size,
                                 int crop_x, int crop_y, int flip, void* stream) {
     if (C < 1 || C > 4 || size < 1 || crop_x < 0 || crop_y < 0 || crop_x + size > S || crop_y + size > S) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(frames_prep_kernel, dim3(ew_blocks_p(n * size * size)), dim3(256), 0, (hipStream_t)stream, frames,
+    VIAI_LAUNCH(frames_prep_kernel, dim3(viai_ew_blocks(n * size * size)), dim3(256), 0, (hipStream_t)stream, frames,
                 reinterpret_cast<f32x4*>(out), n, S, C, size, crop_x, crop_y, flip);
     return viai_launch_status();
 }
@@ -123,19 +116,19 @@ extern "C" int viai_frames_prep(const unsigned char* frames, float* out, long n,
 extern "C" int viai_slice_clips(const float* c, const float* x, const int* start, float* c_out, float* x_out,
                                 int B, int D, int L, int hop, long T_total, long samples, void* stream) {
     if (B < 1 || D < 1 || L < 1 || hop < 1) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(slice_clips_kernel, dim3(ew_blocks_p((long)B * L * (D + hop))), dim3(256), 0, (hipStream_t)stream, c, x, start,
+    VIAI_LAUNCH(slice_clips_kernel, dim3(viai_ew_blocks((long)B * L * (D + hop))), dim3(256), 0, (hipStream_t)stream, c, x, start,
                 c_out, x_out, B, D, L, hop, T_total, samples);
     return viai_launch_status();
 }
 
 extern "C" int viai_ema_update(float* shadow, const float* x, long n, double decay, void* stream) {
     // (1 - decay) in double, then rounded once: 1.0f - 0.9999f would carry a 1.7e-4 relative cancellation error
-    VIAI_LAUNCH(ema_kernel, dim3(ew_blocks_p(n)), dim3(256), 0, (hipStream_t)stream, shadow, x, n, (float)(1.0 - decay));
+    VIAI_LAUNCH(ema_kernel, dim3(viai_ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, shadow, x, n, (float)(1.0 - decay));
     return viai_launch_status();
 }
 
 extern "C" int viai_mel_denorm_amp(const float* S, float* out, long n, float min_level_db, void* stream) {
-    VIAI_LAUNCH(mel_denorm_amp_kernel, dim3(ew_blocks_p(n)), dim3(256), 0, (hipStream_t)stream, S, out, n, min_level_db);
+    VIAI_LAUNCH(mel_denorm_amp_kernel, dim3(viai_ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, S, out, n, min_level_db);
     return viai_launch_status();
 }
 

@@ -500,21 +500,14 @@ __global__ __launch_bounds__(256) void avgpool2d_bwd_kernel(const float* __restr
     }
 }
 
-inline int ew_blocks(long n) {
-    long b = (n + 255) / 256;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 }  // namespace
 
 extern "C" int viai_bilinear_ac_fwd(const float* x, float* y, int N, int IH, int IW, int OH, int OW, int C, void* stream) {
     if (C % 4 != 0 || N <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return (int)hipErrorInvalidValue;
     long total = (long)N * OH * OW * (C / 4);
     const int c4sh = px_shift(C, (long)N * OH * OW);
-    if (c4sh >= 0) VIAI_LAUNCH(bilinear_fwd_px_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y, N, IH, IW, OH, OW, C, c4sh);
-    else VIAI_LAUNCH(bilinear_fwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y, N, IH, IW, OH, OW, C);
+    if (c4sh >= 0) VIAI_LAUNCH(bilinear_fwd_px_kernel, dim3(viai_ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y, N, IH, IW, OH, OW, C, c4sh);
+    else VIAI_LAUNCH(bilinear_fwd_kernel, dim3(viai_ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y, N, IH, IW, OH, OW, C);
     return viai_launch_status();
 }
 
@@ -564,22 +557,22 @@ extern "C" int viai_bilinear_ac_bwd(const float* dy, float* dx, int N, int IH, i
     if (C % 4 != 0 || N <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return (int)hipErrorInvalidValue;
     long total = (long)N * IH * IW * (C / 4);
     const int c4sh = px_shift(C, (long)N * IH * IW);
-    if (c4sh >= 0) VIAI_LAUNCH(bilinear_bwd_px_kernel<6>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, IH, IW, OH, OW, C, c4sh);
-    else VIAI_LAUNCH(bilinear_bwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, IH, IW, OH, OW, C);
+    if (c4sh >= 0) VIAI_LAUNCH(bilinear_bwd_px_kernel<6>, dim3(viai_ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, IH, IW, OH, OW, C, c4sh);
+    else VIAI_LAUNCH(bilinear_bwd_kernel, dim3(viai_ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, IH, IW, OH, OW, C);
     return viai_launch_status();
 }
 
 extern "C" int viai_avgpool_h_fwd(const float* x, float* y, int N, int IH, int W, int C, int k, void* stream) {
     if (C % 4 != 0 || k <= 0 || IH / k <= 0) return (int)hipErrorInvalidValue;
     long total = (long)N * (IH / k) * W * (C / 4);
-    VIAI_LAUNCH(avgpool_h_fwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y, N, IH, W, C, k);
+    VIAI_LAUNCH(avgpool_h_fwd_kernel, dim3(viai_ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y, N, IH, W, C, k);
     return viai_launch_status();
 }
 
 extern "C" int viai_avgpool_h_bwd(const float* dy, float* dx, int N, int IH, int W, int C, int k, void* stream) {
     if (C % 4 != 0 || k <= 0 || IH / k <= 0) return (int)hipErrorInvalidValue;
     long total = (long)N * IH * W * (C / 4);
-    VIAI_LAUNCH(avgpool_h_bwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, IH, W, C, k);
+    VIAI_LAUNCH(avgpool_h_bwd_kernel, dim3(viai_ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, IH, W, C, k);
     return viai_launch_status();
 }
 
@@ -587,7 +580,7 @@ extern "C" int viai_maxpool_fwd(const float* x, float* y, unsigned char* idx, in
     if (C % 4 != 0 || k * k > 255) return (int)hipErrorInvalidValue;
     int OH = (IH + 2 * p - k) / s + 1, OW = (IW + 2 * p - k) / s + 1;
     long total = (long)N * OH * OW * (C / 4);
-    VIAI_LAUNCH(maxpool_fwd_kernel<false>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y, idx, N, IH, IW, OH, OW, C, k, s, p,
+    VIAI_LAUNCH(maxpool_fwd_kernel<false>, dim3(viai_ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y, idx, N, IH, IW, OH, OW, C, k, s, p,
                 (const float*)nullptr, (const float*)nullptr, 0, 0.f, (float*)nullptr);
     return viai_launch_status();
 }
@@ -599,11 +592,11 @@ extern "C" int viai_bn_act_maxpool_fwd(const float* y, const float* scale, const
     int OH = (IH + 2 * p - k) / s + 1, OW = (IW + 2 * p - k) / s + 1;
     long total = (long)N * OH * OW * (C / 4);
     if (k == 3 && s == 2 && p == 1 && total < (1L << 31) - (1L << 24)) {
-        VIAI_LAUNCH(bn_act_maxpool3_fwd_kernel<false>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, y, out, idx, N, IH, IW, OH, OW, C, scale, shift, act, slope,
+        VIAI_LAUNCH(bn_act_maxpool3_fwd_kernel<false>, dim3(viai_ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, y, out, idx, N, IH, IW, OH, OW, C, scale, shift, act, slope,
                     out_amax, (const float*)nullptr, (const float*)nullptr, 0.f, (float*)nullptr, (float*)nullptr);
         return viai_launch_status();
     }
-    VIAI_LAUNCH(maxpool_fwd_kernel<true>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, y, out, idx, N, IH, IW, OH, OW, C, k, s, p,
+    VIAI_LAUNCH(maxpool_fwd_kernel<true>, dim3(viai_ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, y, out, idx, N, IH, IW, OH, OW, C, k, s, p,
                 scale, shift, act, slope, out_amax);
     return viai_launch_status();
 }
@@ -620,7 +613,7 @@ extern "C" int viai_bn_act_maxpool_fwd_twin(const float* y, const float* scale, 
     long total = (long)N * OH * OW * (C / 4);
     if (total >= (1L << 31) - (1L << 24)) return (int)hipErrorInvalidValue;
     const float rad = sqrtf((float)(m_stat > 1 ? m_stat - 1 : 1));
-    VIAI_LAUNCH(bn_act_maxpool3_fwd_kernel<true>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, y, out, idx, N, IH, IW, OH, OW, C, scale, shift, act, slope,
+    VIAI_LAUNCH(bn_act_maxpool3_fwd_kernel<true>, dim3(viai_ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, y, out, idx, N, IH, IW, OH, OW, C, scale, shift, act, slope,
                 out_amax, gamma, beta, rad, out_p16, p_amax);
     return viai_launch_status();
 }
@@ -629,54 +622,54 @@ extern "C" int viai_maxpool_bwd(const float* dy, const unsigned char* idx, float
     if (C % 4 != 0) return (int)hipErrorInvalidValue;
     int OH = (IH + 2 * p - k) / s + 1, OW = (IW + 2 * p - k) / s + 1;
     long total = (long)N * IH * IW * (C / 4);
-    VIAI_LAUNCH(maxpool_bwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, dy, idx, dx, N, IH, IW, OH, OW, C, k, s, p);
+    VIAI_LAUNCH(maxpool_bwd_kernel, dim3(viai_ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, dy, idx, dx, N, IH, IW, OH, OW, C, k, s, p);
     return viai_launch_status();
 }
 
 extern "C" int viai_avgpool_hw_fwd(const float* x, float* y, int N, int P, int C, void* stream) {
-    VIAI_LAUNCH(avgpool_hw_fwd_kernel, dim3(ew_blocks((long)N * C)), dim3(256), 0, (hipStream_t)stream, x, y, N, P, C);
+    VIAI_LAUNCH(avgpool_hw_fwd_kernel, dim3(viai_ew_blocks((long)N * C)), dim3(256), 0, (hipStream_t)stream, x, y, N, P, C);
     return viai_launch_status();
 }
 
 extern "C" int viai_avgpool_hw_bwd(const float* dy, float* dx, int N, int P, int C, void* stream) {
-    VIAI_LAUNCH(avgpool_hw_bwd_kernel, dim3(ew_blocks((long)N * P * C)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, P, C);
+    VIAI_LAUNCH(avgpool_hw_bwd_kernel, dim3(viai_ew_blocks((long)N * P * C)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, P, C);
     return viai_launch_status();
 }
 
 extern "C" int viai_add_relu_fwd(const float* a, const float* b, float* out, long n, void* stream) {
     if (n % 4 != 0) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(add_relu_fwd_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const f32x4*>(a),
+    VIAI_LAUNCH(add_relu_fwd_kernel, dim3(viai_ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const f32x4*>(a),
                 reinterpret_cast<const f32x4*>(b), reinterpret_cast<f32x4*>(out), n / 4);
     return viai_launch_status();
 }
 
 extern "C" int viai_relu_bwd(const float* g, const float* out, float* d, long n, void* stream) {
     if (n % 4 != 0) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(relu_bwd_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const f32x4*>(g),
+    VIAI_LAUNCH(relu_bwd_kernel, dim3(viai_ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const f32x4*>(g),
                 reinterpret_cast<const f32x4*>(out), reinterpret_cast<f32x4*>(d), n / 4);
     return viai_launch_status();
 }
 
 extern "C" int viai_nchw_to_nhwc4(const float* x, float* y, long N, int C, long HW, void* stream) {
     if (C < 1 || C > 4) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(nchw_to_nhwc4_kernel, dim3(ew_blocks(N * HW)), dim3(256), 0, (hipStream_t)stream, x, reinterpret_cast<f32x4*>(y), N, C, HW, (float*)nullptr);
+    VIAI_LAUNCH(nchw_to_nhwc4_kernel, dim3(viai_ew_blocks(N * HW)), dim3(256), 0, (hipStream_t)stream, x, reinterpret_cast<f32x4*>(y), N, C, HW, (float*)nullptr);
     return viai_launch_status();
 }
 // (ABI 15) ... and max |x| into *amax (zero-initialised)
 extern "C" int viai_nchw_to_nhwc4_amax(const float* x, float* y, long N, int C, long HW, float* amax, void* stream) {
     if (C < 1 || C > 4 || amax == nullptr) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(nchw_to_nhwc4_kernel, dim3(ew_blocks(N * HW)), dim3(256), 0, (hipStream_t)stream, x, reinterpret_cast<f32x4*>(y), N, C, HW, amax);
+    VIAI_LAUNCH(nchw_to_nhwc4_kernel, dim3(viai_ew_blocks(N * HW)), dim3(256), 0, (hipStream_t)stream, x, reinterpret_cast<f32x4*>(y), N, C, HW, amax);
     return viai_launch_status();
 }
 
 extern "C" int viai_avgpool2d_fwd(const float* x, float* y, int N, int IH, int IW, int C, int k, int s, int p, void* stream) {
     int OH = (IH + 2 * p - k) / s + 1, OW = (IW + 2 * p - k) / s + 1;
-    VIAI_LAUNCH(avgpool2d_fwd_kernel, dim3(ew_blocks((long)N * OH * OW * C)), dim3(256), 0, (hipStream_t)stream, x, y, N, IH, IW, OH, OW, C, k, s, p);
+    VIAI_LAUNCH(avgpool2d_fwd_kernel, dim3(viai_ew_blocks((long)N * OH * OW * C)), dim3(256), 0, (hipStream_t)stream, x, y, N, IH, IW, OH, OW, C, k, s, p);
     return viai_launch_status();
 }
 
 extern "C" int viai_avgpool2d_bwd(const float* dy, float* dx, int N, int IH, int IW, int C, int k, int s, int p, void* stream) {
     int OH = (IH + 2 * p - k) / s + 1, OW = (IW + 2 * p - k) / s + 1;
-    VIAI_LAUNCH(avgpool2d_bwd_kernel, dim3(ew_blocks((long)N * IH * IW * C)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, IH, IW, OH, OW, C, k, s, p);
+    VIAI_LAUNCH(avgpool2d_bwd_kernel, dim3(viai_ew_blocks((long)N * IH * IW * C)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, IH, IW, OH, OW, C, k, s, p);
     return viai_launch_status();
 }

@@ -59,6 +59,29 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// sum over a block of 256 threads; red: 4 floats of LDS.  The first barrier also fences earlier reads of red.
+__device__ __forceinline__ float block_sum(float v, float* red) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+// grid of an element-wise launch: 256 threads per block, grid-stride beyond 8192 blocks
+static inline int viai_ew_blocks(long n) {
+    long b = (n + 255) / 256;
+    if (b > 8192) b = 8192;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
 // The same sum (different association) without the LDS crossbar: `__shfl_xor` compiles to ds_bpermute_b32, ~100+ cycles each and six
 // of them in a dependent chain per value; four DPP adds (quad swaps, half-row and row mirrors: ALU latency) leave every lane with its
 // 16-lane row sum, four v_readlane fetch the row sums.  For latency-bound kernels that reduce several values per wave.

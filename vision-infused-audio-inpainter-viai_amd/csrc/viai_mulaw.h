@@ -1,4 +1,4 @@
-// mu-law companding shared by viai_mulaw_quantize (wavenet.hip) and the utterance preparation (preprocess.hip): ONE pair of device functions,
+// mu-law companding shared by viai_mulaw_quantize (wavenet_ops.hip) and the utterance preparation (preprocess.hip): ONE pair of device functions,
 // so that a class computed on the fly while trimming is the class viai_mulaw_quantize writes for the same float (utils/librivox.py:66-74).
 #pragma once
 #include "viai_common.h"

@@ -35,11 +35,6 @@ inline int vp_tiles_x(int W) { return (W + VP_TW - 1) / VP_TW; }
 inline int vp_tiles_y(int H) { return (H + VP_TH - 1) / VP_TH; }
 inline bool vp_dim_ok(int H, int W) { return H >= 1 && W >= 1 && H < VP_MAX_DIM && W < VP_MAX_DIM; }
 
-inline int vp_blocks(long n) {
-    long b = (n + 255) / 256;
-    return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-}
-
 // ------------------------------------------------------------------------------------------------ the rule's shared pieces (host and device)
 struct VpGeo { int x0, y0, cw, ch, side, padx, pady; };
 
@@ -393,7 +388,7 @@ extern "C" int viai_video_resize_u8(const unsigned char* src0, const unsigned ch
     hipStream_t st = (hipStream_t)stream;
     const VpSrc s = vp_src(src0, src1, frame_stride, N, H, W, C, bgr);
     VIAI_LAUNCH(vp_table_kernel, dim3(1), dim3(256), 0, st, box, H, W, R, static_cast<int*>(ws));
-    VIAI_LAUNCH(vp_resize_kernel, dim3(vp_blocks((long)n * R * R)), dim3(256), 0, st, s, static_cast<const int*>(ws), frames_index, (long)n, R, out);
+    VIAI_LAUNCH(vp_resize_kernel, dim3(viai_ew_blocks((long)n * R * R)), dim3(256), 0, st, s, static_cast<const int*>(ws), frames_index, (long)n, R, out);
     return viai_launch_status();
 }
 
@@ -407,7 +402,7 @@ extern "C" int viai_video_prepare(const unsigned char* src0, const unsigned char
     hipStream_t st = (hipStream_t)stream;
     const VpSrc s = vp_src(src0, src1, frame_stride, N, H, W, C, bgr);
     VIAI_LAUNCH(vp_table_kernel, dim3(1), dim3(256), 0, st, box, H, W, R, static_cast<int*>(ws));
-    VIAI_LAUNCH(vp_prepare_kernel, dim3(vp_blocks((long)n * size * size)), dim3(256), 0, st, s, static_cast<const int*>(ws), frames_index, (long)n, R,
+    VIAI_LAUNCH(vp_prepare_kernel, dim3(viai_ew_blocks((long)n * size * size)), dim3(256), 0, st, s, static_cast<const int*>(ws), frames_index, (long)n, R,
                 size, crop_x, crop_y, flip, nchw, out);
     return viai_launch_status();
 }

@@ -1,752 +1,20 @@
-// WaveNet vocoder pieces that are not convolutions (gfx950): weight normalisation, the gated activation,
-// residual / skip scaling, the scalar-input first layer, the conditioning up-sampler, the discretised
-// mixture-of-logistics loss and sampler.  The dilated / 1x1 Conv1d layers themselves run on the implicit-GEMM
-// MFMA kernels (conv_igemm.hip, H = 1).  Reference: wavenet_vocoder/{wavenet,modules,mixture}.py.
-// Activations are (B, 1, T, C) NHWC, i.e. (B*T) rows of C channels.
-#include "viai_common.h"
-#include "viai_internal.h"
-#include "viai_mulaw.h"
-
-namespace {
-
-inline int ew_blocks(long n) {
-    long b = (n + 255) / 256;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red) {      // 256 threads
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
-// ---------------------------------------------------------------- weight norm (modules.py:39, torch weight_norm dim=0)
-// w[r][:] = g[r] * v[r][:] / ||v[r]||      one block per row r
-__global__ __launch_bounds__(256) void weight_norm_fwd_kernel(const float* __restrict__ v, const float* __restrict__ g,
-                                                              float* __restrict__ w, float* __restrict__ norm, int L) {
-    __shared__ float red[4];
-    const int r = blockIdx.x;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < L; i += 256) { float t = v[(size_t)r * L + i]; s += t * t; }
-    const float n = sqrtf(block_sum(s, red));
-    const float sc = g[r] / n;
-    for (int i = threadIdx.x; i < L; i += 256) w[(size_t)r * L + i] = v[(size_t)r * L + i] * sc;
-    if (threadIdx.x == 0) norm[r] = n;
-}
-
-// dg[r] = <dw, v>/n ;  dv = g/n * (dw - v * <dw, v>/n^2)
-__global__ __launch_bounds__(256) void weight_norm_bwd_kernel(const float* __restrict__ dw, const float* __restrict__ v,
-                                                              const float* __restrict__ g, const float* __restrict__ norm,
-                                                              float* __restrict__ dv, float* __restrict__ dg, int L, int accumulate) {
-    __shared__ float red[4];
-    const int r = blockIdx.x;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < L; i += 256) s += dw[(size_t)r * L + i] * v[(size_t)r * L + i];
-    const float dot = block_sum(s, red);
-    const float n = norm[r], gs = g[r] / n, k = dot / (n * n);
-    for (int i = threadIdx.x; i < L; i += 256) {
-        float t = gs * (dw[(size_t)r * L + i] - v[(size_t)r * L + i] * k);
-        dv[(size_t)r * L + i] = accumulate ? dv[(size_t)r * L + i] + t : t;
-    }
-    if (threadIdx.x == 0) dg[r] = accumulate ? dg[r] + dot / n : dot / n;
-}
-
-// ---------------------------------------------------------------- gated activation (modules.py:183-201)
-// y, yc: rows of 2*H channels [a | b];  z[row][h] = tanh(a + ca) * sigmoid(b + cb)
-__global__ __launch_bounds__(256) void glu_fwd_kernel(const float* __restrict__ y, const float* __restrict__ yc,
-                                                      float* __restrict__ z, long rows, int H) {
-    const int h4n = H / 4;
-    const long total = rows * h4n;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
-        long r = i / h4n; int h = (int)(i % h4n) * 4;
-        f32x4 a = *reinterpret_cast<const f32x4*>(y + r * 2 * H + h), b = *reinterpret_cast<const f32x4*>(y + r * 2 * H + H + h);
-        if (yc) { a += *reinterpret_cast<const f32x4*>(yc + r * 2 * H + h); b += *reinterpret_cast<const f32x4*>(yc + r * 2 * H + H + h); }
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = tanhf(a[e]) * (1.f / (1.f + expf(-b[e])));
-        *reinterpret_cast<f32x4*>(z + r * H + h) = o;
-    }
-}
-
-// dy[row] = [dz*(1-tanh^2)*sig | dz*tanh*sig*(1-sig)]   (the same tensor is the gradient of y AND of yc)
-__global__ __launch_bounds__(256) void glu_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ y, const float* __restrict__ yc,
-                                                      float* __restrict__ dy, long rows, int H) {
-    const int h4n = H / 4;
-    const long total = rows * h4n;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
-        long r = i / h4n; int h = (int)(i % h4n) * 4;
-        f32x4 a = *reinterpret_cast<const f32x4*>(y + r * 2 * H + h), b = *reinterpret_cast<const f32x4*>(y + r * 2 * H + H + h);
-        if (yc) { a += *reinterpret_cast<const f32x4*>(yc + r * 2 * H + h); b += *reinterpret_cast<const f32x4*>(yc + r * 2 * H + H + h); }
-        f32x4 g = *reinterpret_cast<const f32x4*>(dz + r * H + h), da, db;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float t = tanhf(a[e]), s = 1.f / (1.f + expf(-b[e]));
-            da[e] = g[e] * (1.f - t * t) * s;
-            db[e] = g[e] * t * s * (1.f - s);
-        }
-        *reinterpret_cast<f32x4*>(dy + r * 2 * H + h) = da;
-        *reinterpret_cast<f32x4*>(dy + r * 2 * H + H + h) = db;
-    }
-}
-
-// out = (a + b) * s   (b may be null: out = a * s)
-__global__ __launch_bounds__(256) void add_scale_kernel(const f32x4* __restrict__ a, const f32x4* __restrict__ b, f32x4* __restrict__ o, float s, long n4) {
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256L) o[i] = b ? (a[i] + b[i]) * s : a[i] * s;
-}
-
-__global__ __launch_bounds__(256) void relu_fwd_kernel(const f32x4* __restrict__ a, f32x4* __restrict__ o, long n4) {
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256L) {
-        f32x4 v = a[i];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-        o[i] = v;
-    }
-}
-
-// ---------------------------------------------------------------- scalar-input first conv (wavenet.py:118: Conv1d1x1(1, C))
-// y[p][c] = x[p] * w[c] + b[c]
-__global__ __launch_bounds__(256) void outer_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
-                                                        float* __restrict__ y, long rows, int C) {
-    const int c4n = C / 4;
-    const long total = rows * c4n;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
-        long r = i / c4n; int c = (int)(i % c4n) * 4;
-        f32x4 wv = *reinterpret_cast<const f32x4*>(w + c), bv = *reinterpret_cast<const f32x4*>(b + c);
-        *reinterpret_cast<f32x4*>(y + r * C + c) = x[r] * wv + bv;
-    }
-}
-
-// part[blk][0][c] = sum_p dy[p][c] * x[p];  part[blk][1][c] = sum_p dy[p][c]
-__global__ __launch_bounds__(256) void outer_bwd_part_kernel(const float* __restrict__ dy, const float* __restrict__ x, float* __restrict__ part,
-                                                             long rows, int C, long rows_per_blk) {
-    __shared__ f32x4 r1[256], r2[256];
-    const int tid = threadIdx.x, CG = C / 4;
-    const long row0 = blockIdx.x * rows_per_blk;
-    long row1 = row0 + rows_per_blk; if (row1 > rows) row1 = rows;
-    for (int g0 = 0; g0 < CG; g0 += 256) {
-        const int cgw = min(256, CG - g0), pg = 256 / cgw, cg = tid % cgw, pl = tid / cgw;
-        f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-        // rows in runs of 32 per lane, each run summed on its own: a lane's fp32 error stays that of two short sums (C > 1024 leaves one lane
-        // per column group, up to 1024 rows in a single accumulator: 4.8 x the error of torch's fp32 column sum at 1000 rows)
-        if (pl < pg)
-            for (long r = row0 + pl; r < row1;) {
-                f32x4 p1 = {0.f, 0.f, 0.f, 0.f}, p2 = {0.f, 0.f, 0.f, 0.f};
-                for (int u = 0; u < 32 && r < row1; ++u, r += pg) {
-                    f32x4 g = *reinterpret_cast<const f32x4*>(dy + r * C + (g0 + cg) * 4);
-                    p1 += g * x[r]; p2 += g;
-                }
-                s1 += p1; s2 += p2;
-            }
-        r1[tid] = s1; r2[tid] = s2;
-        __syncthreads();
-        if (tid < cgw) {
-            f32x4 t1 = {0.f, 0.f, 0.f, 0.f}, t2 = {0.f, 0.f, 0.f, 0.f};
-            for (int k = 0; k < pg; ++k) { t1 += r1[k * cgw + tid]; t2 += r2[k * cgw + tid]; }
-            *reinterpret_cast<f32x4*>(part + ((size_t)blockIdx.x * 2 + 0) * C + (g0 + tid) * 4) = t1;
-            *reinterpret_cast<f32x4*>(part + ((size_t)blockIdx.x * 2 + 1) * C + (g0 + tid) * 4) = t2;
-        }
-        __syncthreads();
-    }
-}
-
-__global__ void outer_bwd_final_kernel(const float* __restrict__ part, int nblk, int C, float* dw, float* db, int accumulate) {
-    int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    double s1 = 0.0, s2 = 0.0;
-    for (int b = 0; b < nblk; ++b) { s1 += (double)part[((size_t)b * 2) * C + c]; s2 += (double)part[((size_t)b * 2 + 1) * C + c]; }
-    dw[c] = accumulate ? dw[c] + (float)s1 : (float)s1;
-    db[c] = accumulate ? db[c] + (float)s2 : (float)s2;
-}
-
-// ---------------------------------------------------------------- conditioning up-sampler (wavenet.py:153-164)
-// ConvTranspose2d(1, 1, (KH, S), stride (1, S), padding ((KH-1)/2, 0)) + ReLU on (B, F, T):
-//   out[b][f][t*S + j] = relu(bias + sum_r in[b][f + P - r][t] * w[r][j])
-template <int KH>
-__global__ __launch_bounds__(256) void upsample_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                           float* __restrict__ y, long BF, int F, int T, int S) {
-    constexpr int P = (KH - 1) / 2;
-    const long total = BF * T * S;
-    const float b0 = bias[0];
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
-        long bf = i / ((long)T * S); int to = (int)(i % ((long)T * S));
-        int t = to / S, j = to % S, f = (int)(bf % F);
-        float acc = b0;
-#pragma unroll
-        for (int r = 0; r < KH; ++r) {
-            int fi = f + P - r;
-            if ((unsigned)fi < (unsigned)F) acc += x[(bf - f + fi) * T + t] * w[r * S + j];
-        }
-        y[i] = acc > 0.f ? acc : 0.f;
-    }
-}
-
-// dx[b][f][t] = sum_{r,j} dpre[b][f - P + r][t*S + j] * w[r][j],  dpre = dy * (y > 0)
-template <int KH>
-__global__ __launch_bounds__(256) void upsample_bwd_x_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ w,
-                                                             float* __restrict__ dx, long BF, int F, int T, int S) {
-    constexpr int P = (KH - 1) / 2;
-    const long total = BF * T;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
-        long bf = i / T; int t = (int)(i % T), f = (int)(bf % F);
-        float acc = 0.f;
-#pragma unroll
-        for (int r = 0; r < KH; ++r) {
-            int fo = f - P + r;
-            if ((unsigned)fo >= (unsigned)F) continue;
-            const long base = ((bf - f + fo) * T + t) * S;
-            for (int j = 0; j < S; ++j) { float g = y[base + j] > 0.f ? dy[base + j] : 0.f; acc += g * w[r * S + j]; }
-        }
-        dx[i] = acc;
-    }
-}
-
-// part[blk][r*S + j] = sum dpre[b][f][t*S+j] * x[b][f + P - r][t];  part[blk][KH*S] = sum dpre     (S <= 16)
-template <int KH>
-__global__ __launch_bounds__(256) void upsample_bwd_w_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ x,
-                                                             float* __restrict__ part, long BF, int F, int T, int S) {
-    constexpr int P = (KH - 1) / 2;
-    __shared__ float red[4];
-    float acc[KH * 16 + 1];
-#pragma unroll
-    for (int k = 0; k < KH * 16 + 1; ++k) acc[k] = 0.f;
-    const long total = BF * T;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
-        long bf = i / T; int t = (int)(i % T), f = (int)(bf % F);
-        float xin[KH];
-#pragma unroll
-        for (int r = 0; r < KH; ++r) { int fi = f + P - r; xin[r] = ((unsigned)fi < (unsigned)F) ? x[(bf - f + fi) * T + t] : 0.f; }
-        const long base = (bf * T + t) * S;
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            if (j < S) {
-                float g = y[base + j] > 0.f ? dy[base + j] : 0.f;
-                acc[KH * 16] += g;
-#pragma unroll
-                for (int r = 0; r < KH; ++r) acc[r * 16 + j] += g * xin[r];
-            }
-    }
-    for (int k = 0; k < KH * 16 + 1; ++k) {
-        float s = block_sum(acc[k], red);
-        if (threadIdx.x == 0) part[(size_t)blockIdx.x * (KH * 16 + 1) + k] = s;
-    }
-}
-
-__global__ void upsample_bwd_final_kernel(const float* __restrict__ part, int nblk, int KH, int S, float* dw, float* db, int accumulate) {
-    int k = threadIdx.x;
-    const int W = KH * 16 + 1;
-    if (k >= W) return;
-    double s = 0.0;
-    for (int b = 0; b < nblk; ++b) s += (double)part[(size_t)b * W + k];
-    if (k == KH * 16) { db[0] = accumulate ? db[0] + (float)s : (float)s; return; }
-    int r = k / 16, j = k % 16;
-    if (j < S) dw[r * S + j] = accumulate ? dw[r * S + j] + (float)s : (float)s;
-}
-
-// ---------------------------------------------------------------- discretised mixture of logistics (mixture.py:25-105)
-__device__ __forceinline__ float softplusf(float x) { return x > 20.f ? x : log1pf(expf(x)); }   // torch softplus (threshold 20)
-__device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
-
-// yhat: rows of `pitch` floats, first 3*K are [logit | mean | log_scale]; target y[row]; out loss[row] = -logsumexp_k(...)
-// dyh (optional, same pitch): d(sum_rows wrow[row] * loss[row]) / d yhat
-template <int K>
-__global__ __launch_bounds__(256) void mol_loss_kernel(const float* __restrict__ yhat, const float* __restrict__ y, const float* __restrict__ wrow,
-                                                       float* __restrict__ loss, float* __restrict__ dyh, long rows, int pitch,
-                                                       float num_classes, float log_scale_min) {
-    const float h = 1.f / (num_classes - 1.f), logh2 = logf((num_classes - 1.f) * 0.5f);
-    for (long r = blockIdx.x * 256L + threadIdx.x; r < rows; r += (long)gridDim.x * 256L) {
-        const float* p = yhat + r * pitch;
-        const float yy = y[r];
-        float logit[K], lp[K], dm[K], dls[K];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int k = 0; k < K; ++k) { logit[k] = p[k]; mx = fmaxf(mx, logit[k]); }
-        float se = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) se += expf(logit[k] - mx);
-        const float lse_logit = mx + logf(se);
-        float best = -INFINITY;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const float m = p[K + k], lsr = p[2 * K + k];
-            const bool clamped = lsr < log_scale_min;
-            const float ls = clamped ? log_scale_min : lsr;
-            const float inv = expf(-ls), c = yy - m;
-            const float pin = inv * (c + h), min_ = inv * (c - h), mid = inv * c;
-            float v, gm, gs;                              // value, d/dmean, d/dlog_scale
-            if (yy < -0.999f) {
-                v = pin - softplusf(pin);
-                float d = sigmoidf(-pin);
-                gm = d * (-inv); gs = d * (-pin);
-            } else if (yy > 0.999f) {
-                v = -softplusf(min_);
-                float d = -sigmoidf(min_);
-                gm = d * (-inv); gs = d * (-min_);
-            } else {
-                const float sp = sigmoidf(pin), sm = sigmoidf(min_), cd = sp - sm;
-                if (cd > 1e-5f) {
-                    v = logf(fmaxf(cd, 1e-12f));
-                    const float dp = sp * (1.f - sp) / cd, dn = -sm * (1.f - sm) / cd;
-                    gm = (dp + dn) * (-inv); gs = dp * (-pin) + dn * (-min_);
-                } else {
-                    v = mid - ls - 2.f * softplusf(mid) - logh2;
-                    const float d = 1.f - 2.f * sigmoidf(mid);
-                    gm = d * (-inv); gs = d * (-mid) - 1.f;
-                }
-            }
-            if (clamped) gs = 0.f;
-            lp[k] = v + (logit[k] - lse_logit);
-            dm[k] = gm; dls[k] = gs;
-            best = fmaxf(best, lp[k]);
-        }
-        float s2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) s2 += expf(lp[k] - best);
-        const float lse = best + logf(s2);
-        loss[r] = -lse;
-        if (dyh) {
-            const float wr = wrow ? wrow[r] : 1.f;
-            float* q = dyh + r * pitch;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const float pk = expf(lp[k] - lse);                 // posterior responsibility
-                const float sk = expf(logit[k] - lse_logit);        // prior softmax
-                q[k] = wr * (sk - pk);
-                q[K + k] = wr * (-pk * dm[k]);
-                q[2 * K + k] = wr * (-pk * dls[k]);
-            }
-            for (int k = 3 * K; k < pitch; ++k) q[k] = 0.f;
-        }
-    }
-}
-
-// sample (mixture.py:117-153) with INJECTED uniforms u1[row][K], u2[row] in (1e-5, 1-1e-5)
-template <int K>
-__global__ __launch_bounds__(256) void mol_sample_kernel(const float* __restrict__ yhat, const float* __restrict__ u1, const float* __restrict__ u2,
-                                                         float* __restrict__ out, long rows, int pitch, float log_scale_min) {
-    for (long r = blockIdx.x * 256L + threadIdx.x; r < rows; r += (long)gridDim.x * 256L) {
-        const float* p = yhat + r * pitch;
-        float best = -INFINITY; int arg = 0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            float t = p[k] - logf(-logf(u1[r * K + k]));
-            if (t > best) { best = t; arg = k; }
-        }
-        const float m = p[K + arg], ls = fmaxf(p[2 * K + arg], log_scale_min), u = u2[r];
-        float x = m + expf(ls) * (logf(u) - logf(1.f - u));
-        out[r] = fminf(fmaxf(x, -1.f), 1.f);
-    }
-}
-
-// masked mean: out = sum(loss * mask) / sum(mask)     (loss_functions.py:43-62)
-__global__ __launch_bounds__(256) void masked_mean_kernel(const float* __restrict__ loss, const float* __restrict__ mask, long n, float* out, float* wrow) {
-    __shared__ double r1[4], r2[4];
-    double a = 0.0, b = 0.0;
-    for (long i = threadIdx.x; i < n; i += 256) { float m = mask ? mask[i] : 1.f; a += (double)loss[i] * m; b += m; }
-    a = wave_sum_d(a); b = wave_sum_d(b);
-    if ((threadIdx.x & 63) == 0) { r1[threadIdx.x >> 6] = a; r2[threadIdx.x >> 6] = b; }
-    __syncthreads();
-    const double sa = r1[0] + r1[1] + r1[2] + r1[3], sb = r2[0] + r2[1] + r2[2] + r2[3];
-    if (threadIdx.x == 0) *out = (float)(sa / sb);
-    if (wrow) for (long i = threadIdx.x; i < n; i += 256) wrow[i] = (mask ? mask[i] : 1.f) / (float)sb;
-}
-
-// ---------------------------------------------------------------- masked cross entropy on NHWC rows (loss_functions.py:24-40)
-// One wave per row; lane l holds the float4 column groups 4 l + 256 j (j < NV) of its row, so K = 256 is one 16-byte load per lane.
-constexpr int CE_MAXV = 4;                                            // K <= 1024
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// the row's columns into registers (-inf beyond K), its maximum and sum of exp(x - max): the same instructions in both passes, so the
-// softmax of pass 2 is built from the bits pass 1 saw
-template <int NV>
-__device__ __forceinline__ void ce_row_load(const float* __restrict__ p, int K, int lane, f32x4 (&v)[NV], float& mx, float& se) {
-    mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int c = 4 * lane + 256 * j;
-        if (c < K) v[j] = *reinterpret_cast<const f32x4*>(p + c);
-        else v[j] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        mx = fmaxf(mx, fmaxf(fmaxf(v[j][0], v[j][1]), fmaxf(v[j][2], v[j][3])));
-    }
-    mx = wave_max(mx);
-    se = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) se += expf(v[j][e] - mx);        // exp(-inf) = 0 in the columns beyond K
-    se = wave_sum(se);
-}
-
-// row (b, t) is scored against target (b, t + shift); tgt < 0 means "no target" (the last `shift` rows of a stream)
-__device__ __forceinline__ void ce_row_target(const int* __restrict__ target, const float* __restrict__ mask, long r, int T, int shift,
-                                              int& tgt, float& m) {
-    const long b = r / T;
-    const int t = (int)(r - b * T);
-    if (t + shift < T) {
-        tgt = target[r + shift];
-        m = mask ? mask[b * (T - shift) + t] : 1.f;
-    } else {
-        tgt = -1;
-        m = 0.f;
-    }
-}
-
-// pass 1: loss[row] = logsumexp(row) - row[target]; meff[row] = the mask as applied (0 on the rows without a target)
-template <int NV>
-__global__ __launch_bounds__(256) void masked_ce_rows_kernel(const float* __restrict__ logits, const int* __restrict__ target,
-                                                             const float* __restrict__ mask, float* __restrict__ loss, float* __restrict__ meff,
-                                                             long rows, int T, int K, int pitch, int shift) {
-    const int lane = threadIdx.x & 63;
-    for (long r = blockIdx.x * 4L + (threadIdx.x >> 6); r < rows; r += gridDim.x * 4L) {
-        int tgt; float m;
-        ce_row_target(target, mask, r, T, shift, tgt, m);
-        f32x4 v[NV];
-        float mx, se;
-        ce_row_load<NV>(logits + r * pitch, K, lane, v, mx, se);
-        float xt = 0.f;                                              // the target's logit less the maximum, picked by column number
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) xt += (4 * lane + 256 * j + e == tgt) ? v[j][e] - mx : 0.f;
-        xt = wave_sum(xt);                                           // one non-zero addend at most: exact
-        if (lane == 0) {
-            const bool in_range = tgt >= 0 && tgt < K;
-            // log(se) - (x_t - max), not (max + log(se)) - x_t: the maximum never meets the small term, so rows of large logits keep its bits
-            loss[r] = in_range ? logf(se) - xt : (m != 0.f ? NAN : 0.f);
-            meff[r] = m;
-        }
-    }
-}
-
-// pass 2: dlogits[row][c] = wrow[row] * (softmax(row)[c] - [c == target]); zeros in the columns K .. pitch and on the rows of weight 0
-template <int NV>
-__global__ __launch_bounds__(256) void masked_ce_grad_kernel(const float* __restrict__ logits, const int* __restrict__ target,
-                                                             const float* __restrict__ wrow, float* __restrict__ dlogits,
-                                                             long rows, int T, int K, int pitch, int shift) {
-    const int lane = threadIdx.x & 63;
-    for (long r = blockIdx.x * 4L + (threadIdx.x >> 6); r < rows; r += gridDim.x * 4L) {
-        const long b = r / T;
-        const int t = (int)(r - b * T);
-        const float w = wrow[r];
-        const int tgt = t + shift < T ? target[r + shift] : -1;
-        float* q = dlogits + r * pitch;
-        const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (w == 0.f) {                                              // wave-uniform
-            for (int c = 4 * lane; c < pitch; c += 256) *reinterpret_cast<f32x4*>(q + c) = zero;
-            continue;
-        }
-        f32x4 v[NV];
-        float mx, se;
-        ce_row_load<NV>(logits + r * pitch, K, lane, v, mx, se);
-        const float lg = logf(se);
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int c = 4 * lane + 256 * j;
-            if (c < K) {
-                f32x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = w * (expf((v[j][e] - mx) - lg) - (c + e == tgt ? 1.f : 0.f));
-                *reinterpret_cast<f32x4*>(q + c) = o;
-            } else if (c < pitch) {
-                *reinterpret_cast<f32x4*>(q + c) = zero;
-            }
-        }
-        for (int c = 4 * lane + 256 * NV; c < pitch; c += 256) *reinterpret_cast<f32x4*>(q + c) = zero;
-    }
-}
-
-// ---------------------------------------------------------------- first_conv on class indices (wavenet.py:118 on one-hot rows)
-// wt[k][c] = w[c][k]: 32 x 32 tiles through LDS, both sides coalesced
-__global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ w, float* __restrict__ wt, int R, int Cc) {   // w [R][Cc] -> wt [Cc][R]
-    __shared__ float tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-    for (int i = ty; i < 32; i += 8)
-        if (r0 + i < R && c0 + tx < Cc) tile[i][tx] = w[(size_t)(r0 + i) * Cc + c0 + tx];
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8)
-        if (c0 + i < Cc && r0 + tx < R) wt[(size_t)(c0 + i) * R + r0 + tx] = tile[tx][i];
-}
-
-// h[p][:] = wt[classes[p]][:] + b
-__global__ __launch_bounds__(256) void class_embed_fwd_kernel(const int* __restrict__ classes, const f32x4* __restrict__ wt, const f32x4* __restrict__ b,
-                                                              f32x4* __restrict__ h, long rows, int K, int C4) {
-    const long n = rows * C4;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
-        const long p = i / C4;
-        const int c = (int)(i - p * C4);
-        const int k = classes[p];
-        f32x4 o = f32x4{NAN, NAN, NAN, NAN};
-        if (k >= 0 && k < K) o = wt[(size_t)k * C4 + c] + b[c];
-        h[i] = o;
-    }
-}
-
-// Weight gradient of that layer.  Block (k, s) owns class k in the row segment s: its four waves each scan a quarter of a 2048-row chunk of the
-// class array and list the rows of class k in LDS (ascending inside a wave's quarter, quarters in order), then thread c4 sums the float4 column
-// group c4 of the listed rows of dh in list order, four rows in flight.  part[s][k][:] receives the sum; class_embed_final_kernel adds the
-// segments in order.  Every addition has a fixed place: the same bits on every run, no atomics.  dh is read once in total.
-constexpr int CEB_CHUNK = 2048;
-
-__global__ __launch_bounds__(256) void class_embed_bwd_part_kernel(const float* __restrict__ dh, const int* __restrict__ classes, float* __restrict__ part,
-                                                                   long rows, long seg, int K, int C) {
-    __shared__ int list[4][CEB_CHUNK / 4];
-    __shared__ int cnt[4];
-    const int k = blockIdx.x, s = blockIdx.y;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int C4 = C / 4;
-    const bool own = (int)threadIdx.x < C4;
-    const long r_end = (s + 1) * seg < rows ? (s + 1) * seg : rows;
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (long base = s * seg; base < r_end; base += CEB_CHUNK) {
-        int n = 0;                                                   // wave-uniform
-        const long q0 = base + wave * (CEB_CHUNK / 4);
-        for (int i = 0; i < CEB_CHUNK / 4; i += 64) {
-            const long r = q0 + i + lane;
-            const bool hit = r < r_end && classes[r] == k;
-            const unsigned long long bal = __ballot(hit);
-            if (hit) list[wave][n + __popcll(bal & ((1ull << lane) - 1ull))] = (int)(r - base);
-            n += __popcll(bal);
-        }
-        if (lane == 0) cnt[wave] = n;
-        __syncthreads();
-        if (own) {
-            for (int w = 0; w < 4; ++w) {
-                const int nw = cnt[w];
-                for (int i = 0; i < nw; i += 4) {
-                    f32x4 x[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (i + u < nw) x[u] = *reinterpret_cast<const f32x4*>(dh + (size_t)(base + list[w][i + u]) * C + 4 * threadIdx.x);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (i + u < nw) acc += x[u];
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (own) *reinterpret_cast<f32x4*>(part + ((size_t)s * K + k) * C + 4 * threadIdx.x) = acc;
-}
-
-// dw[c][k] = sum_s part[s][k][c] (s ascending): 32 x 32 tiles through LDS into the parameter's [C][K] layout
-__global__ __launch_bounds__(256) void class_embed_final_kernel(const float* __restrict__ part, float* __restrict__ dw, int S, int K, int C) {
-    __shared__ float tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int k0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-    for (int i = ty; i < 32; i += 8) {
-        float a = 0.f;
-        if (k0 + i < K && c0 + tx < C)
-            for (int s = 0; s < S; ++s) a += part[((size_t)s * K + k0 + i) * C + c0 + tx];
-        tile[i][tx] = a;
-    }
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8)
-        if (c0 + i < C && k0 + tx < K) dw[(size_t)(c0 + i) * K + k0 + tx] = tile[tx][i];
-}
-
-// db[c] = sum_k dw[c][k]: one block per channel
-__global__ __launch_bounds__(256) void class_embed_bias_kernel(const float* __restrict__ dw, float* __restrict__ db, int K) {
-    __shared__ float red[4];
-    float a = 0.f;
-    for (int k = threadIdx.x; k < K; k += 256) a += dw[(size_t)blockIdx.x * K + k];
-    a = block_sum(a, red);
-    if (threadIdx.x == 0) db[blockIdx.x] = a;
-}
-
-// waveform -> mu-law class (utils/librivox.py:66-74)
-__global__ __launch_bounds__(256) void mulaw_quantize_kernel(const float* __restrict__ x, int* __restrict__ cls, long n, float mu) {
-    const float l1p = log1pf(mu);
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) cls[i] = viai_mulaw_class(x[i], mu, l1p);   // viai_mulaw.h
-}
-
-__global__ __launch_bounds__(256) void scale_rows_kernel(float* __restrict__ d, const float* __restrict__ gscale, long n) {
-    const float g = *gscale;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) d[i] *= g;
-}
-
-}  // namespace
-
-extern "C" int viai_weight_norm_fwd(const float* v, const float* g, float* w, float* norm, int rows, int L, void* stream) {
-    VIAI_LAUNCH(weight_norm_fwd_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, v, g, w, norm, L);
-    return viai_launch_status();
-}
-
-extern "C" int viai_weight_norm_bwd(const float* dw, const float* v, const float* g, const float* norm, float* dv, float* dg,
-                                    int rows, int L, int accumulate, void* stream) {
-    VIAI_LAUNCH(weight_norm_bwd_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, dw, v, g, norm, dv, dg, L, accumulate);
-    return viai_launch_status();
-}
-
-extern "C" int viai_glu_fwd(const float* y, const float* yc, float* z, long rows, int H, void* stream) {
-    if (H % 4 != 0) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(glu_fwd_kernel, dim3(ew_blocks(rows * (H / 4))), dim3(256), 0, (hipStream_t)stream, y, yc, z, rows, H);
-    return viai_launch_status();
-}
-
-extern "C" int viai_glu_bwd(const float* dz, const float* y, const float* yc, float* dy, long rows, int H, void* stream) {
-    if (H % 4 != 0) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(glu_bwd_kernel, dim3(ew_blocks(rows * (H / 4))), dim3(256), 0, (hipStream_t)stream, dz, y, yc, dy, rows, H);
-    return viai_launch_status();
-}
-
-extern "C" int viai_add_scale(const float* a, const float* b, float* out, float s, long n, void* stream) {
-    if (n % 4 != 0) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(add_scale_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const f32x4*>(a),
-                reinterpret_cast<const f32x4*>(b), reinterpret_cast<f32x4*>(out), s, n / 4);
-    return viai_launch_status();
-}
-
-extern "C" int viai_relu_fwd(const float* a, float* out, long n, void* stream) {
-    if (n % 4 != 0) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(relu_fwd_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const f32x4*>(a), reinterpret_cast<f32x4*>(out), n / 4);
-    return viai_launch_status();
-}
-
-extern "C" int viai_outer_fwd(const float* x, const float* w, const float* b, float* y, long rows, int C, void* stream) {
-    if (C % 4 != 0) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(outer_fwd_kernel, dim3(ew_blocks(rows * (C / 4))), dim3(256), 0, (hipStream_t)stream, x, w, b, y, rows, C);
-    return viai_launch_status();
-}
-
-extern "C" int viai_outer_bwd_blocks(long rows) { long b = (rows + 1023) / 1024; if (b > 1024) b = 1024; if (b < 1) b = 1; return (int)b; }
-
-extern "C" int viai_outer_bwd(const float* dy, const float* x, float* part, float* dw, float* db, long rows, int C, int accumulate, void* stream) {
-    if (C % 4 != 0) return (int)hipErrorInvalidValue;
-    int nb = viai_outer_bwd_blocks(rows);
-    long rpb = (rows + nb - 1) / nb;
-    VIAI_LAUNCH(outer_bwd_part_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, dy, x, part, rows, C, rpb);
-    VIAI_LAUNCH(outer_bwd_final_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, nb, C, dw, db, accumulate);
-    return viai_launch_status();
-}
-
-extern "C" int viai_upsample_fwd(const float* x, const float* w, const float* bias, float* y, int B, int F, int T, int KH, int S, void* stream) {
-    if (KH != 3 && KH != 1) return (int)hipErrorInvalidValue;
-    long BF = (long)B * F;
-    int blocks = ew_blocks(BF * T * S);
-    if (KH == 3) VIAI_LAUNCH(upsample_fwd_kernel<3>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, w, bias, y, BF, F, T, S);
-    else VIAI_LAUNCH(upsample_fwd_kernel<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, w, bias, y, BF, F, T, S);
-    return viai_launch_status();
-}
-
-extern "C" int viai_upsample_bwd_blocks(void) { return 512; }
-
-extern "C" int viai_upsample_bwd(const float* dy, const float* y, const float* x, const float* w, float* part, float* dx, float* dw, float* db,
-                                 int B, int F, int T, int KH, int S, int accumulate, void* stream) {
-    if ((KH != 3 && KH != 1) || S > 16) return (int)hipErrorInvalidValue;
-    long BF = (long)B * F;
-    hipStream_t st = (hipStream_t)stream;
-    const int nb = 512;
-    if (KH == 3) {
-        if (dx) VIAI_LAUNCH(upsample_bwd_x_kernel<3>, dim3(ew_blocks(BF * T)), dim3(256), 0, st, dy, y, w, dx, BF, F, T, S);
-        VIAI_LAUNCH(upsample_bwd_w_kernel<3>, dim3(nb), dim3(256), 0, st, dy, y, x, part, BF, F, T, S);
-    } else {
-        if (dx) VIAI_LAUNCH(upsample_bwd_x_kernel<1>, dim3(ew_blocks(BF * T)), dim3(256), 0, st, dy, y, w, dx, BF, F, T, S);
-        VIAI_LAUNCH(upsample_bwd_w_kernel<1>, dim3(nb), dim3(256), 0, st, dy, y, x, part, BF, F, T, S);
-    }
-    VIAI_LAUNCH(upsample_bwd_final_kernel, dim3(1), dim3(64), 0, st, part, nb, KH, S, dw, db, accumulate);
-    return viai_launch_status();
-}
-
-extern "C" int viai_mol_loss(const float* yhat, const float* y, const float* mask, float* loss_rows, float* wrow, float* loss,
-                             float* dyhat, long rows, int pitch, int nr_mix, float num_classes, float log_scale_min, void* stream) {
-    if (nr_mix != 10 || pitch < 30) return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
-    // pass 1: per-row losses; masked mean + normalised row weights; pass 2 (if dyhat): gradients with those weights
-    VIAI_LAUNCH(mol_loss_kernel<10>, dim3(ew_blocks(rows)), dim3(256), 0, st, yhat, y, (const float*)nullptr, loss_rows, (float*)nullptr, rows, pitch, num_classes, log_scale_min);
-    VIAI_LAUNCH(masked_mean_kernel, dim3(1), dim3(256), 0, st, loss_rows, mask, rows, loss, wrow);
-    if (dyhat) VIAI_LAUNCH(mol_loss_kernel<10>, dim3(ew_blocks(rows)), dim3(256), 0, st, yhat, y, wrow, loss_rows, dyhat, rows, pitch, num_classes, log_scale_min);
-    return viai_launch_status();
-}
-
-template <int NV>
-static void masked_ce_launch(const float* logits, const int* target, const float* mask, float* loss_rows, float* wrow, float* loss,
-                             float* dlogits, long rows, int T, int K, int pitch, int shift, hipStream_t st) {
-    const long nb = (rows + 3) / 4;
-    const int blocks = (int)(nb > 16384 ? 16384 : (nb < 1 ? 1 : nb));
-    float* meff = wrow + rows;
-    // pass 1: per-row losses; masked mean + normalised row weights in a fixed order; pass 2 (if dlogits): gradients with those weights
-    VIAI_LAUNCH(masked_ce_rows_kernel<NV>, dim3(blocks), dim3(256), 0, st, logits, target, mask, loss_rows, meff, rows, T, K, pitch, shift);
-    VIAI_LAUNCH(masked_mean_kernel, dim3(1), dim3(256), 0, st, (const float*)loss_rows, (const float*)meff, rows, loss, wrow);
-    if (dlogits) VIAI_LAUNCH(masked_ce_grad_kernel<NV>, dim3(blocks), dim3(256), 0, st, logits, target, (const float*)wrow, dlogits, rows, T, K, pitch, shift);
-}
-
-extern "C" int viai_masked_ce_loss(const float* logits, const int* target, const float* mask, float* loss_rows, float* wrow, float* loss,
-                                   float* dlogits, int B, int T, int K, int pitch, int shift, void* stream) {
-    if (B < 1 || T < 1 || K < 4 || K % 4 != 0 || pitch < K || pitch % 4 != 0 || K > 256 * CE_MAXV || shift < 0 || shift >= T)
-        return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
-    const long rows = (long)B * T;
-    switch ((K + 255) / 256) {
-        case 1: masked_ce_launch<1>(logits, target, mask, loss_rows, wrow, loss, dlogits, rows, T, K, pitch, shift, st); break;
-        case 2: masked_ce_launch<2>(logits, target, mask, loss_rows, wrow, loss, dlogits, rows, T, K, pitch, shift, st); break;
-        case 3: masked_ce_launch<3>(logits, target, mask, loss_rows, wrow, loss, dlogits, rows, T, K, pitch, shift, st); break;
-        default: masked_ce_launch<4>(logits, target, mask, loss_rows, wrow, loss, dlogits, rows, T, K, pitch, shift, st); break;
-    }
-    return viai_launch_status();
-}
-
-extern "C" int viai_class_embed_fwd(const int* classes, const float* w, const float* b, float* wt, float* h, long rows, int K, int C, void* stream) {
-    if (rows < 1 || K < 1 || C < 4 || C % 4 != 0) return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
-    VIAI_LAUNCH(transpose_kernel, dim3((K + 31) / 32, (C + 31) / 32), dim3(256), 0, st, w, wt, C, K);
-    VIAI_LAUNCH(class_embed_fwd_kernel, dim3(ew_blocks(rows * (C / 4))), dim3(256), 0, st, classes, reinterpret_cast<const f32x4*>(wt),
-                reinterpret_cast<const f32x4*>(b), reinterpret_cast<f32x4*>(h), rows, K, C / 4);
-    return viai_launch_status();
-}
-
-// row segments of the weight gradient: 2048 rows each (one chunk), at most 64 of them
-extern "C" int viai_class_embed_bwd_segments(long rows) {
-    long s = (rows + CEB_CHUNK - 1) / CEB_CHUNK;
-    if (s > 64) s = 64;
-    if (s < 1) s = 1;
-    return (int)s;
-}
-
-extern "C" int viai_class_embed_bwd(const float* dh, const int* classes, float* part, float* dw, float* db, long rows, int K, int C, void* stream) {
-    if (rows < 1 || K < 1 || K > 65535 || C < 4 || C % 4 != 0 || C > 1024) return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
-    const int S = viai_class_embed_bwd_segments(rows);
-    long seg = (rows + S - 1) / S;
-    seg = (seg + CEB_CHUNK - 1) / CEB_CHUNK * CEB_CHUNK;               // whole chunks, so a chunk never straddles two segments
-    VIAI_LAUNCH(class_embed_bwd_part_kernel, dim3(K, S), dim3(256), 0, st, dh, classes, part, rows, seg, K, C);
-    VIAI_LAUNCH(class_embed_final_kernel, dim3((C + 31) / 32, (K + 31) / 32), dim3(256), 0, st, (const float*)part, dw, S, K, C);
-    VIAI_LAUNCH(class_embed_bias_kernel, dim3(C), dim3(256), 0, st, (const float*)dw, db, K);
-    return viai_launch_status();
-}
-
-extern "C" int viai_mulaw_quantize(const float* x, int* classes, long n, int mu, void* stream) {
-    if (n < 1 || mu < 1) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(mulaw_quantize_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, classes, n, (float)mu);
-    return viai_launch_status();
-}
-
-extern "C" int viai_scale_by_scalar(float* d, const float* gscale, long n, void* stream) {
-    VIAI_LAUNCH(scale_rows_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, d, gscale, n);
-    return viai_launch_status();
-}
-
-extern "C" int viai_mol_sample(const float* yhat, const float* u1, const float* u2, float* out, long rows, int pitch, int nr_mix,
-                               float log_scale_min, void* stream) {
-    if (nr_mix != 10) return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(mol_sample_kernel<10>, dim3(ew_blocks(rows)), dim3(256), 0, (hipStream_t)stream, yhat, u1, u2, out, rows, pitch, log_scale_min);
-    return viai_launch_status();
-}
-
-// =====================================================================================================
+// WaveNet sample-by-sample synthesis, the chain forms (gfx950): the unfused, fused and one-hot (categorical) time step, each with or
+// without a mask of forced steps, and the host dispatch behind viai_wavenet_synth_{step,run}[_forced].  Shared between kernels, once each:
+// the time index (wn_time), the four-term dot (wn_dot4_strict / wn_dot4), the wave-per-row loop of the row-parallel head layers
+// (wn_rows_dot) and the mixture-of-logistics draw of the four heads (viai_mol.h).  wn_gate_kernel / wn_out_kernel and the two halves of
+// wn_stage_kernel, and wn_head_kernel and wn_head_fused_kernel, still hold the same stages twice: built from shared device functions the
+// former ran slower and the latter changed its bits (profiles/wavenet_split_check.json).
+// The training-side kernels (weight norm, GLU, losses, mu-law, ...) are wavenet_ops.hip, the pipelined form is wavenet_pipe.hip.
+//
 // Incremental synthesis (wavenet.py:237-364, conv.py:17-46).  One time step = first conv + per layer two
 // GEMV-batch kernels (gate, then out/skip) + head (two 1x1 layers + MoL sample).  The time index lives in
 // DEVICE memory (`step`), ring-buffer slots are derived from it inside the kernels, so every launch has static
 // arguments and one step can be captured once into a hipGraph and replayed T times.
 // Linearised weights: Wlin[g][j*C + ci] = w[g][ci][j] (conv.py:53-57), taps j = 0..2 read x[t-(2-j)*d].
+#include "viai_common.h"
+#include "viai_internal.h"
+#include "viai_mol.h"
+
 namespace {
 
 constexpr int WN_MAXB = 8;
@@ -755,8 +23,14 @@ constexpr int WN_MAXB = 8;
 // floating-point contraction left to the compiler each instantiation fused another subset of the products into its sums (it packs the streams
 // pairwise: wn_out_kernel<1> had no fused multiply-add, <2> had), so stream b of a 4-stream run differed in the last bits from the 1-stream run
 // on the same inputs.  WN_STRICT_FP, first statement of every NB-templated kernel, switches contraction off there: every product and sum is
-// rounded on its own, in source order, whatever NB is.
+// rounded on its own, in source order, whatever NB is.  The pragma is lexical: an inlined helper carries the setting of its OWN body, so every
+// helper with arithmetic that those kernels call starts with it too, and the kernels without it (one block per stream: wn_first_kernel, the
+// four MoL heads, wn_cat_sample_kernel) call only helpers without it.
 #define WN_STRICT_FP _Pragma("clang fp contract(off)")
+
+// ---- the shared pieces of a time step ---------------------------------------------------------------------------------------------------
+// The time index of every kernel behind the first conv: by value (t_arg >= 0) or from device memory, which the first launch has advanced.
+__device__ __forceinline__ int wn_time(const int* __restrict__ step, int t_arg) { return t_arg >= 0 ? t_arg : *step - 1; }
 
 // Is the input of time step t of stream b given (teacher-forced)?  Without a mask: the common prefix t < n_test (wavenet.py:322-323).  With a
 // mask `forced` (B, T) uint8 (viai_wavenet_synth_run_forced; the test inputs then cover all T steps, n_test == T): the mask's entry.
@@ -764,6 +38,37 @@ __device__ __forceinline__ bool wn_forced(const unsigned char* __restrict__ forc
     return forced != nullptr ? forced[(size_t)b * T + t] != 0 : t < n_test;
 }
 
+// x . w over one 16-byte chunk, x0 w0 + x1 w1 + x2 w2 + x3 w3 in this association.  The regimes, spelled out.  _strict, for the NB-templated
+// kernels: every product and sum rounded.  The plain one, for the one-block-per-stream heads: contraction left to the compiler, as ever.
+__device__ __forceinline__ float wn_dot4_strict(const f32x4 x, const f32x4 w) {
+    WN_STRICT_FP
+    return x[0] * w[0] + x[1] * w[1] + x[2] * w[2] + x[3] * w[3];
+}
+__device__ __forceinline__ float wn_dot4(const f32x4 x, const f32x4 w) { return x[0] * w[0] + x[1] * w[1] + x[2] * w[2] + x[3] * w[3]; }
+
+// A wave per output row, every weight row read once for all NB streams: acc[b] = this lane's part of w_row . act(x[b]), act = ReLU if RELU_IN.
+// wave_sum_dpp finishes the sum.
+template <int NB, bool RELU_IN = false>
+__device__ __forceinline__ void wn_rows_dot(const float* __restrict__ w_row, const float* __restrict__ x, size_t x_stride, int K, int lane,
+                                            float (&acc)[NB]) {
+    WN_STRICT_FP
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[b] = 0.f;
+    for (int k = lane * 4; k < K; k += 256) {
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(w_row + k);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            f32x4 xv = *reinterpret_cast<const f32x4*>(x + b * x_stride + k);
+            if (RELU_IN) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) xv[e] = fmaxf(xv[e], 0.f);
+            }
+            acc[b] += wn_dot4_strict(xv, wv);
+        }
+    }
+}
+
+// ---- the plain form: first conv, gate and out/skip per layer, head --------------------------------------------------------------------------
 // x0[b][:] = cur[b] * w_first + b_first -> ring0[slot(t)];  cur = test_inputs[t] | out[t-1] | 0
 // ONE block.  The time index comes either by value (t_arg >= 0: viai_wavenet_synth_run, the host loop knows it) or from device memory
 // (t_arg < 0: viai_wavenet_synth_step, replayable from a hipGraph): there this kernel also advances it once all of its threads have
@@ -906,10 +211,11 @@ __global__ __launch_bounds__(256) void wn_out_kernel(const float* __restrict__ z
     }
 }
 
+// ---- the MoL head in one block of 16 waves per stream -----------------------------------------------------------------------------------
+// wn_head_kernel and wn_head_fused_kernel keep their stages written out, each in its own text: they leave contraction to the compiler, and
+// which products it fuses depends on how it packs neighbouring rows into two-float instructions.  Built from shared stage functions
+// wn_head_fused_kernel packed its rows the way wn_head_kernel does and its sums changed in the last bits.
 // head: relu -> W1 -> relu -> W2 -> MoL sample with injected uniforms -> out[b][t]; one block of 16 waves per stream.
-// At one block per stream the kernel is a chain of load latencies, so everything that does not depend on the previous stage is
-// fetched up front (uniforms, biases) and every stage has all of its rows in flight at once: a wave takes 16 rows, each read
-// coalesced (16 bytes per lane).  (A row per THREAD, 256 strided loads in sequence: 17.7 us; four rows per trip: 49 us.)
 __global__ __launch_bounds__(1024) void wn_head_kernel(const float* __restrict__ skips, const float* __restrict__ w1, const float* __restrict__ b1,
                                                        const float* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ u1,
                                                        const float* __restrict__ u2, float* __restrict__ out, float* __restrict__ yhat_dbg,
@@ -932,7 +238,7 @@ __global__ __launch_bounds__(1024) void wn_head_kernel(const float* __restrict__
 #pragma unroll
         for (int r = 0; r < RB; ++r) p[r] = *reinterpret_cast<const f32x4*>(w1 + (size_t)min(r1 + r, S - 1) * S + k0);
     }
-    const int t = t_arg >= 0 ? t_arg : *step - 1;
+    const int t = wn_time(step, t_arg);
     for (int k = tid; k < S; k += 1024) { float v = skips[(size_t)b * S + k]; xin[k] = v > 0.f ? v : 0.f; }
     if (tid < K) us[tid] = u1[((size_t)b * T + t) * K + tid];
     if (tid == K) us[K] = u2[(size_t)b * T + t];
@@ -941,7 +247,7 @@ __global__ __launch_bounds__(1024) void wn_head_kernel(const float* __restrict__
     auto batch = [&](const float* __restrict__, const f32x4 (&pre)[RB], const float* x, int, float (&acc)[RB]) {
         const f32x4 xv = k0 < S ? *reinterpret_cast<const f32x4*>(x + k0) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int r = 0; r < RB; ++r) acc[r] = k0 < S ? pre[r][0] * xv[0] + pre[r][1] * xv[1] + pre[r][2] * xv[2] + pre[r][3] * xv[3] : 0.f;
+        for (int r = 0; r < RB; ++r) acc[r] = k0 < S ? wn_dot4(pre[r], xv) : 0.f;
     };
     auto finish = [&](const float (&acc)[RB], float bv, int h0, int n_out, auto&& emit) {
 #pragma unroll
@@ -962,16 +268,7 @@ __global__ __launch_bounds__(1024) void wn_head_kernel(const float* __restrict__
     __syncthreads();
     if (r2 < OC) { batch(w2, p, hid, OC, acc); finish(acc, bv2, r2, OC, logit_out); }
     __syncthreads();
-    if (tid == 0) {
-        float best = -INFINITY; int arg = 0;
-        for (int k = 0; k < K; ++k) {
-            float v = yo[k] - logf(-logf(us[k]));
-            if (v > best) { best = v; arg = k; }
-        }
-        const float m = yo[K + arg], ls = fmaxf(yo[2 * K + arg], log_scale_min), u = us[K];
-        float x = m + expf(ls) * (logf(u) - logf(1.f - u));
-        out[(size_t)b * T + t] = fminf(fmaxf(x, -1.f), 1.f);
-    }
+    if (tid == 0) out[(size_t)b * T + t] = viai_mol_draw(yo, us, us[K], K, log_scale_min);
 }
 
 // any S / out_ch: a row per thread (the first version of the head)
@@ -982,7 +279,7 @@ __global__ __launch_bounds__(256) void wn_head_generic_kernel(const float* __res
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* xin = sm; float* hid = sm + S; float* yo = sm + 2 * S;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int t = t_arg >= 0 ? t_arg : *step - 1;
+    const int t = wn_time(step, t_arg);
     for (int k = tid; k < S; k += 256) { float v = skips[(size_t)b * S + k]; xin[k] = v > 0.f ? v : 0.f; }
     __syncthreads();
     for (int h = tid; h < S; h += 256) {
@@ -998,17 +295,8 @@ __global__ __launch_bounds__(256) void wn_head_generic_kernel(const float* __res
         if (yhat_dbg) yhat_dbg[((size_t)b * T + t) * OC + o] = acc;
     }
     __syncthreads();
-    if (tid == 0) {
-        const int K = OC / 3;
-        float best = -INFINITY; int arg = 0;
-        for (int k = 0; k < K; ++k) {
-            float v = yo[k] - logf(-logf(u1[((size_t)b * T + t) * K + k]));
-            if (v > best) { best = v; arg = k; }
-        }
-        const float m = yo[K + arg], ls = fmaxf(yo[2 * K + arg], log_scale_min), u = u2[(size_t)b * T + t];
-        float x = m + expf(ls) * (logf(u) - logf(1.f - u));
-        out[(size_t)b * T + t] = fminf(fmaxf(x, -1.f), 1.f);
-    }
+    const int K = OC / 3;
+    if (tid == 0) out[(size_t)b * T + t] = viai_mol_draw(yo, u1 + ((size_t)b * T + t) * K, u2[(size_t)b * T + t], K, log_scale_min);
 }
 
 // ---- fused stages (ABI 7): ONE dependent launch per layer instead of two -----------------------------------------------------------
@@ -1249,7 +537,7 @@ __global__ __launch_bounds__(1024) void wn_head_fused_kernel(const float* __rest
     const float bvs = bsk[min(r0 + (lane & (RB - 1)), S - 1)];
     const float bv1 = b1[min(r0 + (lane & (RB - 1)), S - 1)], bv2 = b2[min(r0 + (lane & (RB - 1)), OC - 1)];
     const float prev = (!first_skip && r0 < S) ? skips[(size_t)b * S + min(r0 + (lane & (RB - 1)), S - 1)] : 0.f;
-    const int t = t_arg >= 0 ? t_arg : *step - 1;
+    const int t = wn_time(step, t_arg);
     if (tid < K) us[tid] = u1[((size_t)b * T + t) * K + tid];
     if (tid == K) us[K] = u2[(size_t)b * T + t];
     float acc[RB];
@@ -1257,7 +545,7 @@ __global__ __launch_bounds__(1024) void wn_head_fused_kernel(const float* __rest
     if (r0 < S) {
         const f32x4 zv = k0 < H ? *reinterpret_cast<const f32x4*>(z + (size_t)b * H + k0) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int r = 0; r < RB; ++r) acc[r] = k0 < H ? p[r][0] * zv[0] + p[r][1] * zv[1] + p[r][2] * zv[2] + p[r][3] * zv[3] : 0.f;
+        for (int r = 0; r < RB; ++r) acc[r] = k0 < H ? wn_dot4(p[r], zv) : 0.f;
     }
     if (r0 < S && k0 < S) {                                    // W1's rows: in flight across the skip reductions
 #pragma unroll
@@ -1275,7 +563,7 @@ __global__ __launch_bounds__(1024) void wn_head_fused_kernel(const float* __rest
     if (r0 < S) {
         const f32x4 xv = k0 < S ? *reinterpret_cast<const f32x4*>(xin + k0) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int r = 0; r < RB; ++r) acc[r] = k0 < S ? p[r][0] * xv[0] + p[r][1] * xv[1] + p[r][2] * xv[2] + p[r][3] * xv[3] : 0.f;
+        for (int r = 0; r < RB; ++r) acc[r] = k0 < S ? wn_dot4(p[r], xv) : 0.f;
     }
     if (r0 < OC && k0 < S) {
 #pragma unroll
@@ -1292,7 +580,7 @@ __global__ __launch_bounds__(1024) void wn_head_fused_kernel(const float* __rest
     if (r0 < OC) {
         const f32x4 xv = k0 < S ? *reinterpret_cast<const f32x4*>(hid + k0) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int r = 0; r < RB; ++r) acc[r] = k0 < S ? p[r][0] * xv[0] + p[r][1] * xv[1] + p[r][2] * xv[2] + p[r][3] * xv[3] : 0.f;
+        for (int r = 0; r < RB; ++r) acc[r] = k0 < S ? wn_dot4(p[r], xv) : 0.f;
 #pragma unroll
         for (int r = 0; r < RB; ++r) {
             const float v = wave_sum_dpp(acc[r]) + __shfl(bv2, r, 64);
@@ -1300,16 +588,7 @@ __global__ __launch_bounds__(1024) void wn_head_fused_kernel(const float* __rest
         }
     }
     __syncthreads();
-    if (tid == 0) {
-        float best = -INFINITY; int arg = 0;
-        for (int k = 0; k < K; ++k) {
-            float v = yo[k] - logf(-logf(us[k]));
-            if (v > best) { best = v; arg = k; }
-        }
-        const float m = yo[K + arg], ls = fmaxf(yo[2 * K + arg], log_scale_min), u = us[K];
-        float x = m + expf(ls) * (logf(u) - logf(1.f - u));
-        out[(size_t)b * T + t] = fminf(fmaxf(x, -1.f), 1.f);
-    }
+    if (tid == 0) out[(size_t)b * T + t] = viai_mol_draw(yo, us, us[K], K, log_scale_min);
 }
 
 // ---- the head as three row-parallel launches -------------------------------------------------------------------------------------
@@ -1324,20 +603,11 @@ __global__ __launch_bounds__(256) void wn_head_rows_kernel(const float* __restri
     WN_STRICT_FP
     const int o = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (o >= nrows) return;
-    float acc[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) acc[b] = 0.f;
     float pre = 0.f;
     if (mode == 0 && !first_skip && lane < NB) pre = out[(size_t)lane * nrows + o];
     const float bv = bias[o];
-    for (int k = lane * 4; k < K; k += 256) {
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(w + (size_t)o * K + k);
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + (size_t)b * K + k);
-            acc[b] += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
-        }
-    }
+    float acc[NB];
+    wn_rows_dot<NB>(w + (size_t)o * K, x, (size_t)K, K, lane, acc);
     const float r5 = 0.70710678118654752f;
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
@@ -1356,39 +626,28 @@ __global__ __launch_bounds__(256) void wn_head_sample_kernel(const float* __rest
                                                              float log_scale_min) {
     __shared__ float yo[256];
     const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int t = t_arg >= 0 ? t_arg : *step - 1;
+    const int t = wn_time(step, t_arg);
     const int K3 = OC / 3;
     for (int o = wave; o < OC; o += 4) {
         float acc = 0.f;
-        for (int k = lane * 4; k < S; k += 256) {
-            const f32x4 wv = *reinterpret_cast<const f32x4*>(w2 + (size_t)o * S + k);
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(hid + (size_t)b * S + k);
-            acc += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
-        }
+        for (int k = lane * 4; k < S; k += 256)
+            acc += wn_dot4(*reinterpret_cast<const f32x4*>(hid + (size_t)b * S + k), *reinterpret_cast<const f32x4*>(w2 + (size_t)o * S + k));
         const float v = wave_sum_dpp(acc) + b2[o];
         if (lane == 0) { yo[o] = v; if (yhat_dbg) yhat_dbg[((size_t)b * T + t) * OC + o] = v; }
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        float best = -INFINITY; int arg = 0;
-        for (int k = 0; k < K3; ++k) {
-            const float v = yo[k] - logf(-logf(u1[((size_t)b * T + t) * K3 + k]));
-            if (v > best) { best = v; arg = k; }
-        }
-        const float m = yo[K3 + arg], ls = fmaxf(yo[2 * K3 + arg], log_scale_min), u = u2[(size_t)b * T + t];
-        const float x = m + expf(ls) * (logf(u) - logf(1.f - u));
-        out[(size_t)b * T + t] = fminf(fmaxf(x, -1.f), 1.f);
-    }
+    if (threadIdx.x == 0) out[(size_t)b * T + t] = viai_mol_draw(yo, u1 + ((size_t)b * T + t) * K3, u2[(size_t)b * T + t], K3, log_scale_min);
 }
 
 // ---- categorical network: first conv, head rows, softmax + draw ---------------------------------------------------------------------------
 // First conv, a wave per output channel c, every weight row read once for all streams.  Dense form: lane holds 4 of the K <= 256 columns, the
 // wave sum has a fixed order.  Class form: lane b copies one element for stream b (skipped when `dense_only`: the fused stage 0 gathers itself).
+// The dense loop is wn_rows_dot's with a row pointer and a skip condition per stream; it stays written out here.
 template <int NB>
 __global__ __launch_bounds__(256) void wn_cat_first_kernel(const WnCatIn in, const float* __restrict__ bias, float* __restrict__ ring, int ring_len,
                                                            const int* __restrict__ step, int t_arg, int C, int dense_only) {
     WN_STRICT_FP
-    const int t = t_arg >= 0 ? t_arg : *step - 1;
+    const int t = wn_time(step, t_arg);
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= C) return;
     const int slot = t % ring_len;
@@ -1405,8 +664,7 @@ __global__ __launch_bounds__(256) void wn_cat_first_kernel(const WnCatIn in, con
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             if (in.forced != nullptr && wn_cat_class_form_of(in, t, b)) continue;      // a class stream in a mixed step: gathered below
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(wn_cat_row(in, t, b) + k);
-            acc[b] += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
+            acc[b] += wn_dot4_strict(*reinterpret_cast<const f32x4*>(wn_cat_row(in, t, b) + k), wv);
         }
     }
 #pragma unroll
@@ -1426,16 +684,7 @@ __global__ __launch_bounds__(256) void wn_cat_rows_kernel(const float* __restric
     if (o >= nrows) return;
     const float bv = bias[o];
     float acc[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) acc[b] = 0.f;
-    for (int k = lane * 4; k < K; k += 256) {
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(w + (size_t)o * K + k);
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + (size_t)b * K + k);
-            acc[b] += fmaxf(xv[0], 0.f) * wv[0] + fmaxf(xv[1], 0.f) * wv[1] + fmaxf(xv[2], 0.f) * wv[2] + fmaxf(xv[3], 0.f) * wv[3];
-        }
-    }
+    wn_rows_dot<NB, true>(w + (size_t)o * K, x, (size_t)K, K, lane, acc);
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         const float v = wave_sum_dpp(acc[b]) + bv;
@@ -1454,7 +703,7 @@ __global__ __launch_bounds__(256) void wn_cat_sample_kernel(const float* __restr
     __shared__ double carry[4];
     __shared__ int cnt[4];
     const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int t = t_arg >= 0 ? t_arg : *step - 1;
+    const int t = wn_time(step, t_arg);
     const bool live = tid < K;
     const float x = live ? logits[(size_t)b * K + tid] : -INFINITY;
     const float uu = quantize ? u[(size_t)b * T + t] : 0.f;
@@ -1463,9 +712,7 @@ __global__ __launch_bounds__(256) void wn_cat_sample_kernel(const float* __restr
         if (row && live) row[tid] = x;
         return;
     }
-    float m = x;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    float m = wave_max(x);
     if (lane == 0) red[wave] = m;
     __syncthreads();
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
@@ -1495,15 +742,7 @@ __global__ __launch_bounds__(256) void wn_cat_sample_kernel(const float* __restr
     if (row && live) row[tid] = tid == cls ? 1.f : 0.f;             // wavenet.py:355-356
 }
 
-__global__ __launch_bounds__(256) void mulaw_decode_kernel(const int* __restrict__ cls, float* __restrict__ out, long n, float mu) {
-    const float l1p = log1pf(mu);
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
-        const float y = 2.f * (float)cls[i] / mu - 1.f;
-        const float mag = expm1f(fabsf(y) * l1p) / mu;              // ((1 + mu)^|y| - 1) / mu
-        out[i] = y < 0.f ? -mag : mag;
-    }
-}
-
+// ---- host: one time step as launches --------------------------------------------------------------------------------------------------------
 WnCatIn wn_cat_in(const viai_wn_synth* s, const unsigned char* forced) {
     WnCatIn in{};
     in.forced = forced;
@@ -1544,6 +783,28 @@ bool wn_fused_ok(const viai_wn_synth* s) {
     return true;
 }
 
+// dynamic LDS of wn_head_kernel / wn_head_fused_kernel (WnHeadLds)
+size_t wn_head_lds_bytes(const viai_wn_synth* s) { return (2 * s->S + ((s->out_ch + 3) & ~3) + s->out_ch / 3 + 1) * sizeof(float); }
+
+// the argument of stage l: it writes z into zb[l & 1] and reads layer l - 1's from the other buffer
+WnStage wn_stage_args(const viai_wn_synth* s, int l, float* const (&zb)[2], int t_arg, const unsigned char* forced) {
+    const viai_wn_layer* L = s->layers;
+    WnStage a{};
+    if (s->categorical && l == 0) a.cat = wn_cat_in(s, forced);
+    a.ring = L[l].ring; a.ring_len = L[l].ring_len; a.dil = L[l].dilation;
+    a.w = L[l].w_stage; a.bias = L[l].b_stage; a.wc = L[l].w_c; a.cond = s->cond; a.gadd = L[l].g_add;
+    a.z_out = zb[l & 1]; a.z_in = zb[(l & 1) ^ 1];
+    a.w_first = s->w_first; a.b_first = s->b_first; a.test_inputs = s->test_inputs; a.n_test = s->n_test; a.out = s->out;
+    a.ring_w = L[l].ring; a.skips = s->skips;
+    if (l > 0) {
+        a.ring_prev = L[l - 1].ring; a.prev_len = L[l - 1].ring_len;
+        a.w_out = L[l - 1].w_out; a.b_out = L[l - 1].b_out; a.w_skip = L[l - 1].w_skip; a.b_skip = L[l - 1].b_skip;
+        a.first_skip = (l == 1) ? 1 : 0;
+    }
+    a.step = s->step; a.t_arg = t_arg; a.l = l; a.C = s->C; a.H = s->G / 2; a.S = s->S; a.cin = s->cin; a.T = s->T; a.B = s->B; a.forced = forced;
+    return a;
+}
+
 template <int NB>
 int wn_step_fused_impl(const viai_wn_synth* s, int t_arg, hipStream_t st, const unsigned char* forced) {
     const int C = s->C, H = s->G / 2, S = s->S, n = s->n_layers;
@@ -1552,45 +813,31 @@ int wn_step_fused_impl(const viai_wn_synth* s, int t_arg, hipStream_t st, const 
     const bool cat = s->categorical != 0;
     if (cat && wn_cat_dense_at(s, t_arg, forced))
         VIAI_LAUNCH(wn_cat_first_kernel<NB>, dim3((C + 3) / 4), dim3(256), 0, st, wn_cat_in(s, forced), s->b_first, L[0].ring, L[0].ring_len, s->step, t_arg, C, 1);
-    float* zb[2] = {s->z, s->z2};
+    float* const zb[2] = {s->z, s->z2};
     for (int l = 0; l < n; ++l) {
-        WnStage a{};
-        a.ring = L[l].ring; a.ring_len = L[l].ring_len; a.dil = L[l].dilation;
-        a.w = L[l].w_stage; a.bias = L[l].b_stage; a.wc = L[l].w_c; a.cond = s->cond; a.gadd = L[l].g_add;
-        a.z_out = zb[l & 1]; a.z_in = zb[(l & 1) ^ 1];
-        a.w_first = s->w_first; a.b_first = s->b_first; a.test_inputs = s->test_inputs; a.n_test = s->n_test; a.out = s->out;
-        a.ring_w = L[l].ring; a.skips = s->skips;
-        if (l > 0) {
-            a.ring_prev = L[l - 1].ring; a.prev_len = L[l - 1].ring_len;
-            a.w_out = L[l - 1].w_out; a.b_out = L[l - 1].b_out; a.w_skip = L[l - 1].w_skip; a.b_skip = L[l - 1].b_skip;
-            a.first_skip = (l == 1) ? 1 : 0;
-        }
-        a.step = s->step; a.t_arg = t_arg; a.l = l; a.C = C; a.H = H; a.S = S; a.cin = s->cin; a.T = s->T; a.B = s->B; a.forced = forced;
+        const WnStage a = wn_stage_args(s, l, zb, t_arg, forced);
         const int nb = H + (l == 0 ? 1 : (C + S + 3) / 4);
-        if (cat && l == 0) {
-            a.cat = wn_cat_in(s, forced);
-            VIAI_LAUNCH((wn_stage_kernel<NB, true>), dim3(nb), dim3(256), 0, st, a);
-        } else {
-            VIAI_LAUNCH(wn_stage_kernel<NB>, dim3(nb), dim3(256), 0, st, a);
-        }
+        if (cat && l == 0) VIAI_LAUNCH((wn_stage_kernel<NB, true>), dim3(nb), dim3(256), 0, st, a);
+        else VIAI_LAUNCH(wn_stage_kernel<NB>, dim3(nb), dim3(256), 0, st, a);
     }
-    if (cat) {                                     // the last layer's skip rows (in place), then the categorical head
-        VIAI_LAUNCH(wn_head_rows_kernel<NB>, dim3((S + 3) / 4), dim3(256), 0, st, L[n - 1].w_skip, L[n - 1].b_skip, (const float*)zb[(n - 1) & 1], H, s->skips, S, 0, n == 1 ? 1 : 0);
+    const float* zlast = zb[(n - 1) & 1];
+    const int first = n == 1 ? 1 : 0;
+    auto skip_rows = [&] {                         // the last layer's skip rows, in place
+        VIAI_LAUNCH(wn_head_rows_kernel<NB>, dim3((S + 3) / 4), dim3(256), 0, st, L[n - 1].w_skip, L[n - 1].b_skip, zlast, H, s->skips, S, 0, first);
+    };
+    if (cat) {
+        skip_rows();
         wn_cat_head<NB>(s, t_arg, st);
-        return viai_launch_status();
-    }
-    if (S <= H && s->out_ch <= 256) {
-        float* zlast = zb[(n - 1) & 1];
+    } else if (S <= H && s->out_ch <= 256) {
         float* hid = zb[n & 1];                    // (B, S) fits the (B, H) buffer; the next time step's stage 0 overwrites it
-        VIAI_LAUNCH(wn_head_rows_kernel<NB>, dim3((S + 3) / 4), dim3(256), 0, st, L[n - 1].w_skip, L[n - 1].b_skip, (const float*)zlast, H, s->skips, S, 0, n == 1 ? 1 : 0);
+        skip_rows();
         VIAI_LAUNCH(wn_head_rows_kernel<NB>, dim3((S + 3) / 4), dim3(256), 0, st, s->w_l1, s->b_l1, (const float*)s->skips, S, hid, S, 1, 0);
         VIAI_LAUNCH(wn_head_sample_kernel, dim3(s->B), dim3(256), 0, st, (const float*)hid, s->w_l2, s->b_l2, s->u1, s->u2, s->out, s->yhat_dbg, s->step, t_arg, S,
                     s->out_ch, s->T, s->log_scale_min);
-        return viai_launch_status();
+    } else {
+        VIAI_LAUNCH(wn_head_fused_kernel, dim3(s->B), dim3(1024), wn_head_lds_bytes(s), st, s->skips, zlast, L[n - 1].w_skip, L[n - 1].b_skip, first, H,
+                    s->w_l1, s->b_l1, s->w_l2, s->b_l2, s->u1, s->u2, s->out, s->yhat_dbg, s->step, t_arg, S, s->out_ch, s->T, s->log_scale_min);
     }
-    VIAI_LAUNCH(wn_head_fused_kernel, dim3(s->B), dim3(1024), (2 * S + ((s->out_ch + 3) & ~3) + s->out_ch / 3 + 1) * sizeof(float), st,
-                s->skips, zb[(n - 1) & 1], L[n - 1].w_skip, L[n - 1].b_skip, n == 1 ? 1 : 0, H, s->w_l1, s->b_l1, s->w_l2, s->b_l2, s->u1, s->u2,
-                s->out, s->yhat_dbg, s->step, t_arg, S, s->out_ch, s->T, s->log_scale_min);
     return viai_launch_status();
 }
 
@@ -1617,7 +864,7 @@ int wn_step_impl(const viai_wn_synth* s, int t_arg, hipStream_t st, const unsign
         return viai_launch_status();
     }
     if (S <= 256 && s->out_ch <= 256)
-        VIAI_LAUNCH(wn_head_kernel, dim3(s->B), dim3(1024), (2 * S + ((s->out_ch + 3) & ~3) + s->out_ch / 3 + 1) * sizeof(float), st, s->skips, s->w_l1, s->b_l1, s->w_l2, s->b_l2,
+        VIAI_LAUNCH(wn_head_kernel, dim3(s->B), dim3(1024), wn_head_lds_bytes(s), st, s->skips, s->w_l1, s->b_l1, s->w_l2, s->b_l2,
                     s->u1, s->u2, s->out, s->yhat_dbg, s->step, t_arg, S, s->out_ch, s->T, s->log_scale_min);
     else
         VIAI_LAUNCH(wn_head_generic_kernel, dim3(s->B), dim3(256), (2 * S + s->out_ch) * sizeof(float), st, s->skips, s->w_l1, s->b_l1, s->w_l2, s->b_l2,
@@ -1635,29 +882,36 @@ bool wn_valid(const viai_wn_synth* s) {
     return true;
 }
 
-int wn_step(const viai_wn_synth* s, int t_arg, hipStream_t st, const unsigned char* forced = nullptr) {
-    if (wn_fused_ok(s)) {
-        switch (s->B) {
-        case 1: return wn_step_fused_impl<1>(s, t_arg, st, forced);
-        case 2: return wn_step_fused_impl<2>(s, t_arg, st, forced);
-        case 4: return wn_step_fused_impl<4>(s, t_arg, st, forced);
-        case 8: return wn_step_fused_impl<8>(s, t_arg, st, forced);
-        default: return (int)hipErrorInvalidValue;
-        }
-    }
-    switch (s->B) {
-    case 1: return wn_step_impl<1>(s, t_arg, st, forced);
-    case 2: return wn_step_impl<2>(s, t_arg, st, forced);
-    case 4: return wn_step_impl<4>(s, t_arg, st, forced);
-    case 8: return wn_step_impl<8>(s, t_arg, st, forced);
-    default: return (int)hipErrorInvalidValue;
-    }
-}
-
 // a mask needs given inputs at all T steps (wn_valid has checked that the one-hot network has classes or rows where n_test > 0)
 bool wn_forced_valid(const viai_wn_synth* s, const unsigned char* forced) {
     if (forced == nullptr) return true;
     return s->T >= 1 && s->n_test == s->T && (s->categorical || s->test_inputs != nullptr);
+}
+
+// the only switch over the stream counts the kernels are instantiated for: f(std::integral_constant<int, NB>)
+template <class F>
+int wn_for_streams(int B, F&& f) {
+    switch (B) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return (int)hipErrorInvalidValue;
+    }
+}
+
+// what the four entry points do: time steps t0 .. t0 + n - 1 with the index passed by value, or (t0 = -1) the one step whose index is on the device
+int wn_run(const viai_wn_synth* s, const unsigned char* forced, int t0, int n, void* stream) {
+    if (!wn_valid(s) || !wn_forced_valid(s, forced) || (t0 >= 0 && (n < 0 || t0 + n > s->T))) return (int)hipErrorInvalidValue;
+    const bool fused = wn_fused_ok(s);
+    for (int t = t0; t < t0 + n; ++t) {
+        const int e = wn_for_streams(s->B, [&](auto nb) {
+            constexpr int NB = decltype(nb)::value;
+            return fused ? wn_step_fused_impl<NB>(s, t, (hipStream_t)stream, forced) : wn_step_impl<NB>(s, t, (hipStream_t)stream, forced);
+        });
+        if (e != 0) return e;
+    }
+    return 0;
 }
 
 }  // namespace
@@ -1672,37 +926,14 @@ extern "C" int viai_wn_categorical_ok(const viai_wn_synth* s) {
     return 1;
 }
 
-extern "C" int viai_mulaw_decode(const int* classes, float* out, long n, int mu, void* stream) {
-    if (n < 0 || mu < 1) return (int)hipErrorInvalidValue;
-    if (n == 0) return 0;
-    VIAI_LAUNCH(mulaw_decode_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, classes, out, n, (float)mu);
-    return viai_launch_status();
-}
-
-extern "C" int viai_wavenet_synth_step(const viai_wn_synth* s, void* stream) {
-    if (!wn_valid(s)) return (int)hipErrorInvalidValue;
-    return wn_step(s, -1, (hipStream_t)stream);
-}
+extern "C" int viai_wavenet_synth_step(const viai_wn_synth* s, void* stream) { return wn_run(s, nullptr, -1, 1, stream); }
 
 extern "C" int viai_wavenet_synth_run(const viai_wn_synth* s, int t0, int n_steps, void* stream) {
-    if (!wn_valid(s) || t0 < 0 || n_steps < 0 || t0 + n_steps > s->T) return (int)hipErrorInvalidValue;
-    for (int t = t0; t < t0 + n_steps; ++t) {
-        const int e = wn_step(s, t, (hipStream_t)stream);
-        if (e != 0) return e;
-    }
-    return 0;
+    return t0 < 0 ? (int)hipErrorInvalidValue : wn_run(s, nullptr, t0, n_steps, stream);
 }
 
-extern "C" int viai_wavenet_synth_step_forced(const viai_wn_synth* s, const unsigned char* forced, void* stream) {
-    if (!wn_valid(s) || !wn_forced_valid(s, forced)) return (int)hipErrorInvalidValue;
-    return wn_step(s, -1, (hipStream_t)stream, forced);
-}
+extern "C" int viai_wavenet_synth_step_forced(const viai_wn_synth* s, const unsigned char* forced, void* stream) { return wn_run(s, forced, -1, 1, stream); }
 
 extern "C" int viai_wavenet_synth_run_forced(const viai_wn_synth* s, const unsigned char* forced, int t0, int n_steps, void* stream) {
-    if (!wn_valid(s) || !wn_forced_valid(s, forced) || t0 < 0 || n_steps < 0 || t0 + n_steps > s->T) return (int)hipErrorInvalidValue;
-    for (int t = t0; t < t0 + n_steps; ++t) {
-        const int e = wn_step(s, t, (hipStream_t)stream, forced);
-        if (e != 0) return e;
-    }
-    return 0;
+    return t0 < 0 ? (int)hipErrorInvalidValue : wn_run(s, forced, t0, n_steps, stream);
 }

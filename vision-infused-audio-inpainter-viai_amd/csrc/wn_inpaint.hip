@@ -1,18 +1,11 @@
 // Waveform inpainting around the WaveNet synthesis loop (gfx950): cut per-stream windows [receptive field | gap] out of a clip and its up-sampled
-// conditioning, and put the generated samples back.  The loop itself is csrc/wavenet.hip with a mask of forced steps
+// conditioning, and put the generated samples back.  The loop itself is the synthesis chain of csrc/wavenet.hip with a mask of forced steps
 // (viai_wavenet_synth_run_forced): the R samples in front of a gap are teacher-forced (they fill the dilated convs' ring buffers the way
 // wavenet.py:322-327 does with test_inputs), the gap runs free.  Window arithmetic: include/viai_hip.h, DESIGN.md 11.2f.
 #include "viai_common.h"
 #include "viai_internal.h"
 
 namespace {
-
-inline int wi_blocks(long n) {
-    long b = (n + 255) / 256;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 
 // item i = (row r = b L + t, column group c of q): the conditioning row's float4 number c; the item with c == 0 also writes the row's input
 // and its mask entry.  Source time s = w[b] + t; outside [0, n) the clip is silent (0.0 / `silence` / a zero conditioning row).
@@ -75,7 +68,7 @@ extern "C" int viai_wn_window_gather(const float* wav, const int* classes, const
         return (int)hipErrorInvalidValue;
     if (cond != nullptr && (cond_out == nullptr || cin < 4 || cin % 4 != 0)) return (int)hipErrorInvalidValue;
     const int q = cond != nullptr ? cin / 4 : 1;
-    VIAI_LAUNCH(wn_window_gather_kernel, dim3(wi_blocks((long)B * L * q)), dim3(256), 0, (hipStream_t)stream, wav, classes, cond, w, len, x_out, cls_out,
+    VIAI_LAUNCH(wn_window_gather_kernel, dim3(viai_ew_blocks((long)B * L * q)), dim3(256), 0, (hipStream_t)stream, wav, classes, cond, w, len, x_out, cls_out,
                 cond_out, forced, B, n, L, R, cin, q, silence_class);
     return viai_launch_status();
 }
@@ -84,6 +77,6 @@ extern "C" int viai_wn_splice(const float* wav, const float* gen, const int* g0,
                               void* stream) {
     if (B < 1 || n < 1 || L < 1 || R < 0 || fade < 0 || wav == nullptr || gen == nullptr || g0 == nullptr || len == nullptr || out == nullptr)
         return (int)hipErrorInvalidValue;
-    VIAI_LAUNCH(wn_splice_kernel, dim3(wi_blocks((long)B * n)), dim3(256), 0, (hipStream_t)stream, wav, gen, g0, len, out, B, n, L, R, fade);
+    VIAI_LAUNCH(wn_splice_kernel, dim3(viai_ew_blocks((long)B * n)), dim3(256), 0, (hipStream_t)stream, wav, gen, g0, len, out, B, n, L, R, fade);
     return viai_launch_status();
 }
