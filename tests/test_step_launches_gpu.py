@@ -111,8 +111,9 @@ def _fused_key(entry, desc):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- census
-def run_census(model, steps=1):
-    """launch records of `steps` optimize_parameters calls of `model`: a list of dicts, deduplicated, values only"""
+def run_census(model, steps=1, run=None):
+    """launch records of `steps` calls of `run(i)` (default: model.optimize_parameters): a list of dicts, deduplicated, values only"""
+    run = model.optimize_parameters if run is None else run
     from viai_amd import _lib
     lib = _lib.load()
     names = [n for n, (_r, at) in _lib.SIGNATURES.items()
@@ -146,7 +147,7 @@ def run_census(model, steps=1):
             orig[n] = fn
             setattr(lib, n, wrap(n, fn))
         for i in range(steps):
-            model.optimize_parameters(i)
+            run(i)
         torch.cuda.synchronize()
     finally:
         for n, fn in orig.items():
@@ -313,8 +314,11 @@ def _wgrad64(g, x64_of, dy64_of, w64):
     return acc
 
 
-def replay(rec, gen):
-    """one census launch again on fresh operands: (family seen, {quantity: error}); raises on a library error"""
+def replay(rec, gen, worst_tile=None, keep=None):
+    """one census launch again on fresh operands: (family seen, {quantity: error}); raises on a library error.
+    `worst_tile`: the tile error to use instead of _worst_tile (tests/test_inference_launches_gpu.py: clipped tiles); `keep`: a dict that
+    receives the forward's fp64 operands and results (x, w, bias, act, y, truth), for a second opinion on the same operands"""
+    worst_tile = _worst_tile if worst_tile is None else worst_tile
     from oracle import viai_oracle as O
     from viai_amd import _lib, ops
     lib = _lib.load()
@@ -393,7 +397,9 @@ def replay(rec, gen):
         ytrue = _act64(g.fwd64(x64_cat(xv, x2, imgs), w64) + (bias.double().cpu().view(1, -1, 1, 1) if bias is not None else 0), act)
         yk = _nchw64(y[imgs])
         errs["y"] = _relerr(yk, ytrue)
-        errs["tile"] = _worst_tile(yk, ytrue)
+        errs["tile"] = worst_tile(yk, ytrue)
+        if keep is not None:
+            keep.update(x=x64_cat(xv, x2, imgs), w=w64, bias=bias.double().cpu() if bias is not None else None, act=act, y=yk, truth=ytrue)
         if subset and not g.frames and act == 0 and bias is None:
             # <y, gy> = <x, dgrad(gy)> over the whole batch, the data gradient from the plain kernel of the same layer
             gy = uni(tuple(y.shape))
@@ -429,7 +435,7 @@ def replay(rec, gen):
         if dx2 is not None:
             dk = torch.cat((dk, _nchw64(dx2[imgs])), 1)
         errs["dx"] = _relerr(dk, dtrue)
-        errs["tile"] = _worst_tile(dk, dtrue)
+        errs["tile"] = worst_tile(dk, dtrue)
         if subset:
             # <x, dx> = <fwd(x), dy> over the whole batch, the forward from the plain kernel of the same layer
             x = uni((g.N, g.IH, g.IW, g.C1))
