@@ -556,6 +556,46 @@ int viai_gap_detect(const float* wav, const int* lengths, long stride, int B, lo
 int viai_gap_detect_host(const float* wav, const int* lengths, long stride, int B, long n, float threshold, float clip, int min_len,
                          int merge_within, int K, int* count, int* start, int* length);
 
+/* ---- short gaps: Burg autoregressive interpolation (csrc/ar_fill.hip, csrc/viai_ar_rule.h; additive to ABI v20) ----
+ * Every listed gap of every row is filled from the clean samples on its two sides: an all-pole model is fitted to each side (Burg's method),
+ * extrapolated into the gap -- forward from the left, backward from the right -- and the two predictions are cross-faded.  fp64 arithmetic of
+ * + - * / only, each operation rounded once, every sum in a stated order: the kernel and the host mirror call the same functions of
+ * csrc/viai_ar_rule.h and give the same bits.
+ * For row b, len = clamp(lengths[b], 0, n) (n when lengths is NULL) and listed = min(max(count[b], 0), K).  Gap k < listed is
+ * [s, e) = [start[b][k], start[b][k] + length[b][k]), L = e - s:
+ *   SKIPPED   (filled = 0, no sample written) when L < 1, L > max_len, s < 0 or e > len; filled[b][k] = 0 for k >= listed as well.
+ *   CONTEXT   left [max(s - context, start[b][k-1] + length[b][k-1] if k > 0, 0), s), right [e, min(e + context, start[b][k+1] if k + 1 < listed,
+ *             len)); an empty interval where the bounds cross.  The neighbours count whether they are skipped or not, so with lists in position
+ *             order a context never holds a sample of a listed gap: what a block reads is disjoint from what every block writes, and out may
+ *             be wav itself.  A non-finite context sample reads as 0.0.
+ *   ORDER     a side with C context samples has p = min(order, C / 2) (integer division) and is usable iff p >= 1.
+ *   FIT       Burg on x[0 .. C), the right side on its context time-reversed (x[j] = row[e + C - 1 - j]): f = x[1:], b = x[:-1], a = [1]; per
+ *             stage k = -2 <f, b> / (<f, f> + <b, b>), 0 when the denominator is 0; a <- [a, 0] + k reverse([a, 0]); f' = (f + k b)[1:],
+ *             b' = (b + k f)[:-1]; p stages.  No clamp, no window.
+ *   SUMS      each of the three dot products of a stage: 256 partials, partial t the terms i = t, t + 256, ... in ascending i from +0.0, each
+ *             term one rounded product added with one rounded sum; then the adjacent pairwise tree: for o = 1, 2, 4, ..., 128,
+ *             part[t] += part[t + o] for every t that is a multiple of 2 o.
+ *   EXTRAPOLATE  x^[i] = 0.0 - sum_{j = 1 .. p} a_j x^[i - j], i = 0 .. L - 1, seeded with the last p context samples.  The sum: 64 partials,
+ *             partial l = a_{l+1} x^[i-l-1] (+ a_{l+65} x^[i-l-65]) over the terms with j <= p, +0.0 without one, then the same tree over 64.
+ *             fwd[i] is step i from the left; bwd[i] is step L - 1 - i of the reversed right side.
+ *   BLEND     u = (i + 0.5) / L, w = 1 - (u u) (3 - 2 u), out = w fwd + (1 - w) bwd, rounded to fp32 once.  Left side only: out = fwd; right
+ *             only: out = bwd; neither: out = 0.0.
+ *   filled    1 both sides, 2 left only, 3 right only, 4 no context (zeros written), 0 skipped or not listed.
+ * wav (B, stride) fp32, lengths (B,), count (B,), start / length (B, K) int32 and filled (B, K) int32 in DEVICE memory, as viai_gap_detect leaves
+ * them; out (B, out_stride) fp32: ONLY the samples of filled gaps are written, so the caller copies wav to out first or passes out = wav.  ONE
+ * launch, one block of 256 threads per (row, gap index), no atomics, no workspace, nothing synced; dynamic LDS
+ * 8 (max(4 context, 2 (128 + max_len)) + 540) bytes per block, 135 392 at the limits.
+ * Refuses with hipErrorInvalidValue before any launch: a NULL pointer (lengths excepted); B or K < 1; B K > 2^31 - 1; n < 1 or n >= 2^31;
+ * stride or out_stride < n; order outside 1 .. 128; context outside 2 .. 4096; max_len outside 1 .. 4096; wav or out not 4-byte aligned.       */
+int viai_ar_fill(const float* wav, const int* lengths, long stride, int B, long n, const int* count, const int* start, const int* length, int K,
+                 int order, int context, int max_len, float* out, long out_stride, int* filled, void* stream);
+/* the same rule with plain loops from the same header, every pointer in HOST memory.  Same refusals (the alignment rule apart).                */
+int viai_ar_fill_host(const float* wav, const int* lengths, long stride, int B, long n, const int* count, const int* start, const int* length,
+                      int K, int order, int context, int max_len, float* out, long out_stride, int* filled);
+/* the fit alone, for pinning: x (C,) fp32 in HOST memory, 0 <= C <= 4096 -> a[0 .. order] fp64 (a[0] = 1, zeros behind a[p]) and
+ * *p = min(order, C / 2).  Refuses a NULL pointer, C outside 0 .. 4096, order outside 1 .. 128.                                                */
+int viai_ar_fit_host(const float* x, int C, int order, double* a, int* p);
+
 /* ---- video front end: motion crop, square pad, resize (csrc/video_prep.hip; additive to ABI v20) ----
  * Raw uint8 frames and flow maps of any H x W in, the blocks the generator's visual branch consumes out: `find_cluster`, `crop_image` and
  * `padding_square` of Data_loaders/Image_preprocess.py:168-229,256-268 and the resize / flip / normalise / crop of

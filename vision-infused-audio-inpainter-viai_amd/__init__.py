@@ -13,6 +13,7 @@ name; the top-level `viai_amd/` shim maps the import name onto it).
   metrics   how good an inpainted clip is: gap SNR / SI-SDR, mel L1 / PSNR / log-spectral distance / SSIM, inpainting_report
   wav_resample  clips at any sample rate: Resampler (polyphase, HIP), gap_at_rate, inpaint_at_rate
   gap_detect    where a clip is damaged: find_gaps (dropouts, clipping, non-finite samples; HIP), find_gaps_host, repair
+  ar_fill       short gaps without a network: Burg autoregressive interpolation, ar_fill (HIP), ar_fill_host, ar_fit_host
   video     raw frames and flow maps -> the visual branch's blocks: motion_box, resize_u8, prepare, VideoFrontEnd (HIP), motion_box_host
   optical_flow  raw frames -> TV-L1 flow -> the 8-bit flow maps `video` takes: tvl1, encode_u8, flow_u8 (HIP), tvl1_host, encode_u8_host
   wav_io    WAV in, WAV out: parse_wav, decode_pcm / encode_pcm / patch_pcm (HIP) and their _host mirrors, read_wav, write_wav, save_wav, repair_file
@@ -35,4 +36,7 @@ def __getattr__(name):
                 "read_wav", "write_wav", "save_wav", "repair_file"):
         from . import wav_io
         return getattr(wav_io, name)
+    if name in ("ar_fill_host", "ar_fit_host"):
+        from . import ar_fill
+        return getattr(ar_fill, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

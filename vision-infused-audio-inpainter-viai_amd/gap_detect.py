@@ -2,7 +2,7 @@
 
     find_gaps        runs of non-finite, silent or clipped samples of every row of a batch -> Gaps(count, start, length) on the device
     find_gaps_host   the same rule on a numpy array, in plain C++ on the host (`viai_gap_detect_host`): no GPU needed
-    repair           `find_gaps` + one `AudioInpainter` call per gap index
+    repair           `find_gaps` + one `AudioInpainter` call per gap index; with `ar_below`, gaps shorter than that go to `ar_fill` first
 
 The rule (include/viai_hip.h states it in full): a sample is damaged when it is not finite, or |x| <= threshold, or (clip > 0 and |x| >= clip).
 Maximal runs of damaged samples inside a row's length are kept when they are at least `min_len` long; kept runs at most `merge_within` samples
@@ -115,7 +115,23 @@ def find_gaps_host(wav, lengths=None, threshold=0.0, clip=0.0, min_len=64, merge
     return Gaps(count, start, length)
 
 
-def repair(inpainter, wav, gaps=None, uniforms=None, fade=0, sample_rate=None, **find_gaps_kwargs):
+def _without_filled(count, start, length, filled):
+    """the host lists with the entries whose `filled` code is 1 .. 4 taken out and the rest moved to the front, zeros behind"""
+    B, K = start.shape
+    count, start, length = count.clone(), start.clone(), length.clone()
+    for b in range(B):
+        keep = [k for k in range(int(count[b])) if int(filled[b, k]) == 0]
+        if len(keep) == int(count[b]):
+            continue
+        s, l = start[b, keep].clone(), length[b, keep].clone()
+        start[b], length[b] = 0, 0
+        start[b, :len(keep)], length[b, :len(keep)] = s, l
+        count[b] = len(keep)
+    return count, start, length
+
+
+def repair(inpainter, wav, gaps=None, uniforms=None, fade=0, sample_rate=None, ar_below=0, ar_order=32, ar_context=1024, ar_lengths=None,
+           **find_gaps_kwargs):
     """Detect the gaps of wav (B, n) and regenerate them with `inpainter` (an `AudioInpainter`).  Returns (waveform, Gaps).
 
     gaps       a `Gaps` from an earlier `find_gaps` (tensors or arrays); without it `find_gaps(wav, **find_gaps_kwargs)` runs.
@@ -124,6 +140,13 @@ def repair(inpainter, wav, gaps=None, uniforms=None, fade=0, sample_rate=None, *
     sample_rate  None (the default): wav is at the front end's rate and `inpainter` is called directly, exactly as before this argument existed.
                A rate: pass k is `inpaint_at_rate(inpainter, wav, sample_rate, start[:, k], length[:, k], ...)`, which calls the inpainter
                directly when the rate is the front end's; the overflow rule and the single copy of the lists to the host are the same.
+    ar_below   0 (the default): every gap goes to the inpainter, exactly as before this argument existed.  A length: gaps SHORTER than
+               ar_below samples are filled first by one `ar_fill` launch (Burg autoregressive interpolation, `viai_amd.ar_fill`; order
+               ar_order, context ar_context, max_len = min(ar_below - 1, 4096)) from the host copy of the lists; the entries it filled
+               (`filled` 1 .. 4, read back once) leave the lists, the rest move to the front, and the passes below run over what remains, on
+               a clip whose short gaps already hold plausible signal.  When nothing remains no pass runs, `inpainter` may be None and its
+               limits on rows and hops do not apply.  ar_lengths: (B,) row lengths for `ar_fill` (contexts stop there); default: the
+               `lengths` the detection was given, else n.
 
     count, start and length come to the host ONCE (one synchronisation).  If any row has more gaps than the lists hold (count > K) a ValueError
     names the rows and nothing is repaired: an overflowing detection is never half repaired.  Then pass k = 0 .. max(count) - 1 calls
@@ -138,8 +161,12 @@ def repair(inpainter, wav, gaps=None, uniforms=None, fade=0, sample_rate=None, *
     if wav.dim() != 2:
         raise ValueError("repair: wav is (B, n)")
     B = wav.size(0)
+    if int(ar_below) != ar_below or ar_below < 0:
+        raise ValueError("repair: ar_below is a length in samples, 0 for no autoregressive fill")
     if gaps is None:
         gaps = find_gaps(wav, **find_gaps_kwargs)
+        if ar_lengths is None:
+            ar_lengths = find_gaps_kwargs.get("lengths")
     elif find_gaps_kwargs:
         raise ValueError("repair: gaps given, so nothing is detected: %s unused" % ", ".join(sorted(find_gaps_kwargs)))
     gaps = Gaps(*gaps)
@@ -153,10 +180,21 @@ def repair(inpainter, wav, gaps=None, uniforms=None, fade=0, sample_rate=None, *
     if over:
         raise ValueError("repair: rows %s hold %s gaps, the lists hold %d: detect with a larger max_gaps, min_len or merge_within"
                          % (over, [int(count[b]) for b in over], K))
+    out = wav
+    filled_any = False
+    if ar_below > 1 and B > 0 and K > 0 and int(count.max()) > 0:
+        from .ar_fill import MAX_LEN, ar_fill
+        out, filled = ar_fill(wav, (count.to(torch.int32), start.to(torch.int32), length.to(torch.int32)), lengths=ar_lengths,
+                              order=ar_order, context=ar_context, max_len=min(int(ar_below) - 1, MAX_LEN))
+        count, start, length = _without_filled(count, start, length, filled.cpu())
+        filled_any = True
     passes = int(count.max()) if B > 0 else 0
+    if passes > 0 and inpainter is None:
+        left = {b: [int(v) for v in length[b, :int(count[b])]] for b in range(B) if int(count[b]) > 0}
+        raise ValueError("repair: no inpainter, and rows %s still hold gaps of %s samples: pass an inpainter or a larger ar_below"
+                         % (sorted(left), [left[b] for b in sorted(left)]))
     if uniforms is not None and len(uniforms) < passes:
         raise ValueError("repair: %d passes, uniforms for %d" % (passes, len(uniforms)))
-    out = wav
     for k in range(passes):
         u = None if uniforms is None else uniforms[k]
         if sample_rate is None:
@@ -164,6 +202,6 @@ def repair(inpainter, wav, gaps=None, uniforms=None, fade=0, sample_rate=None, *
         else:
             from .wav_resample import inpaint_at_rate
             out = inpaint_at_rate(inpainter, out, sample_rate, start[:, k].contiguous(), length[:, k].contiguous(), uniforms=u, fade=fade)
-    if passes == 0:
+    if passes == 0 and not filled_any:
         out = wav.float().clone()
     return out, gaps
