@@ -1,4 +1,5 @@
-"""Shared helpers of the direct tests of the non-conv passes (test_bn_passes_gpu.py, test_pool_passes_gpu.py, test_loss_opt_passes_gpu.py).
+"""Shared helpers of the direct tests of the non-conv passes (test_bn_passes_gpu.py, test_pool_passes_gpu.py, test_loss_opt_passes_gpu.py,
+test_contrastive_pipeline_passes_gpu.py; contrastive_common.py draws its inputs from uniform() here).
 
 Every test there calls one C-ABI entry point (include/viai_hip.h) on inputs from the oracle's counter-based generators and compares with a plain
 fp64 restatement on the CPU.  Two kinds of assertion:
