@@ -596,6 +596,48 @@ int viai_ar_fill_host(const float* wav, const int* lengths, long stride, int B, 
  * *p = min(order, C / 2).  Refuses a NULL pointer, C outside 0 .. 4096, order outside 1 .. 128.                                                */
 int viai_ar_fit_host(const float* x, int C, int order, double* a, int* p);
 
+/* ---- clicks: impulsive damage found in a prediction residual (csrc/click_detect.hip, csrc/viai_click_rule.h; additive to ABI v20) ----
+ * A click is neither silent nor clipped nor non-finite, so viai_gap_detect cannot see it.  Here an all-pole model is fitted to a stretch of the
+ * signal, the signal is run through the inverse (prediction-error) filter, and a click is where the squared residual stands far above its own
+ * robust scale.  fp64 arithmetic of + - * / and comparisons only, each operation rounded once, every sum in a stated order (no sqrt, no median):
+ * the kernels and the host mirror call the same functions of csrc/viai_click_rule.h and csrc/viai_ar_rule.h and give the same lists.
+ * For row b, len = clamp(lengths[b], 0, n) (n when lengths is NULL).  The row is cut into the tiles of viai_gap_detect (VIAI_GAP_DETECT_TILE = 4096
+ * samples).  For the tile [t0, t0 + C), C <= 4096, xs(i) the row's sample i in fp64 with a non-finite one read as 0.0:
+ *   FIT       p = min(order, C / 2) (integer division); a[0 .. p] is Burg's fit of viai_ar_fill (FIT and SUMS above, unchanged) on the tile's own C
+ *             samples xs(t0 .. t0 + C - 1).  p < 1: nothing in the tile is judged.
+ *   RESIDUAL  every sample g = t0 + i of the tile with g >= p is JUDGED: e = sum_{j = 0 .. p} a[j] xs(g - j), accumulated from +0.0 in ascending j,
+ *             each term one rounded product added with one rounded sum; the sum reaches back into the previous tile's samples.  q = e e.  Samples
+ *             with g < p (the head of the row) are not judged.
+ *   SCALE     var_0 = sum(q) / cnt over the judged samples of the tile, cnt an integer converted to double; then `passes` times (0 .. 4)
+ *             var_{r+1} = sum(q | q <= kk var_r) / count(q <= kk var_r), a count of 0 leaving var as it was (and var_0 = 0.0 when cnt = 0).
+ *             kk = (double)k (double)k.  Each sum: 256 partials, partial t the tile-local indices i = t, t + 256, ... in ascending i from +0.0 (the
+ *             samples that do not take part are left out), then the adjacent pairwise tree of SUMS above.
+ *   FLAG      a judged sample is flagged when q > kk max(var, ff), ff = (double)floor (double)floor: floor is an amplitude below which nothing
+ *             is a click.  A non-finite sample is always flagged, judged or not.
+ *   GUARD     the damage mask is the flags widened by `guard` samples on both sides: sample i is damaged when a flag lies in
+ *             [i - guard, i + guard].  The widening crosses tiles and never leaves [0, len).  A flag is always judged by the tile that holds the
+ *             sample, and the widening works on the flags alone.
+ *   RUNS      the mask goes through steps 1 to 4 of viai_gap_detect's rule with "damaged" read from the mask: min_len, merge_within, K, count the
+ *             true number.  count (B,), start and length (B, K) int32: the tensors of viai_gap_detect, with the same meaning, and what
+ *             viai_ar_fill and viai_pcm_patch read.
+ * The lists are exact integers, the same from run to run and for a row alone or in any batch.  Joining them with the lists of viai_gap_detect
+ * into one is not done here.                                                                                                                  */
+/* bytes of workspace for one call: the raw flags, the mask (1 bit per sample each) and viai_gap_detect's table per tile.  0 for arguments the
+ * call itself refuses (B, n or K < 1, n >= 2^31, more than 2^31 - 1 tiles in the batch).                                                       */
+long viai_click_detect_ws_bytes(int B, long n, int K);
+/* wav (B, stride) fp32 and lengths (B,) int32 or NULL in DEVICE memory; count, start, length in DEVICE memory; ws: viai_click_detect_ws_bytes(B, n,
+ * K) bytes of device memory, 8-byte aligned, overwritten.  FOUR launches for the whole batch: one block of 256 threads per tile (fit, residual,
+ * scale, raw flags; 67 744 bytes of dynamic LDS, two blocks per CU), one wave per tile (widening, mask, summary), then launches 2 and 3 of
+ * viai_gap_detect.  No atomics, nothing allocated, nothing syncs; rows need 4-byte alignment only; no sample at or beyond len is read.
+ * Refuses with hipErrorInvalidValue before any launch: wav, count, start, length or ws NULL; B, n or K < 1; n >= 2^31; stride < n; order outside
+ * 1 .. 128; k not > 0 or not finite; passes outside 0 .. 4; guard outside 0 .. 64; a negative or NaN floor; min_len < 1; merge_within < 0; wav
+ * not 4-byte or ws not 8-byte aligned; more than 2^31 - 1 tiles.                                                                              */
+int viai_click_detect(const float* wav, const int* lengths, long stride, int B, long n, int order, float k, int passes, int guard, float floor,
+                      int min_len, int merge_within, int K, int* count, int* start, int* length, void* ws, void* stream);
+/* the same rule with plain loops from the same headers, every pointer in HOST memory.  Same refusals (ws and the alignment rules apart).       */
+int viai_click_detect_host(const float* wav, const int* lengths, long stride, int B, long n, int order, float k, int passes, int guard,
+                           float floor, int min_len, int merge_within, int K, int* count, int* start, int* length);
+
 /* ---- video front end: motion crop, square pad, resize (csrc/video_prep.hip; additive to ABI v20) ----
  * Raw uint8 frames and flow maps of any H x W in, the blocks the generator's visual branch consumes out: `find_cluster`, `crop_image` and
  * `padding_square` of Data_loaders/Image_preprocess.py:168-229,256-268 and the resize / flip / normalise / crop of

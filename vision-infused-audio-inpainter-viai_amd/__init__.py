@@ -14,6 +14,8 @@ name; the top-level `viai_amd/` shim maps the import name onto it).
   wav_resample  clips at any sample rate: Resampler (polyphase, HIP), gap_at_rate, inpaint_at_rate
   gap_detect    where a clip is damaged: find_gaps (dropouts, clipping, non-finite samples; HIP), find_gaps_host, repair
   ar_fill       short gaps without a network: Burg autoregressive interpolation, ar_fill (HIP), ar_fill_host, ar_fit_host
+  click_detect  where a clip holds clicks: find_clicks (outliers of an AR prediction residual; HIP), find_clicks_host, declick, declick_host,
+                declick_file
   video     raw frames and flow maps -> the visual branch's blocks: motion_box, resize_u8, prepare, VideoFrontEnd (HIP), motion_box_host
   optical_flow  raw frames -> TV-L1 flow -> the 8-bit flow maps `video` takes: tvl1, encode_u8, flow_u8 (HIP), tvl1_host, encode_u8_host
   wav_io    WAV in, WAV out: parse_wav, decode_pcm / encode_pcm / patch_pcm (HIP) and their _host mirrors, read_wav, write_wav, save_wav, repair_file
@@ -39,4 +41,7 @@ def __getattr__(name):
     if name in ("ar_fill_host", "ar_fit_host"):
         from . import ar_fill
         return getattr(ar_fill, name)
+    if name in ("find_clicks", "find_clicks_host", "declick", "declick_host", "declick_file"):
+        from . import click_detect
+        return getattr(click_detect, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -18,16 +18,13 @@
 
 #include "viai_common.h"
 #include "viai_ar_rule.h"
+#include "viai_ar_fit.h"                                         // the stage loop of the fit and its plain-loop form: shared with click_detect.hip
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int AR_THREADS = AR_PARTS;
-constexpr int AR_COEF = AR_MAX_ORDER + 1;                       // a_0 .. a_128
-constexpr int AR_SMALL = 2 * 2 * AR_COEF + 4 * 6;               // doubles behind the big region: a[side][buffer][AR_COEF], red[wave][6]
-static_assert(AR_THREADS == 256 && AR_LANES == 64, "four waves of 64: the tree of the rule");
-static_assert(AR_COEF <= AR_THREADS && 2 * AR_MAX_ORDER <= AR_THREADS, "one thread per coefficient and per seed");
+constexpr int AR_SMALL = ar_small_doubles(2);                   // doubles behind the big region: a[side][buffer][AR_COEF], red[wave][6]
 
 inline long ar_big_doubles(int context, int max_len) {
     const long fit = 4L * context, pred = 2L * (AR_MAX_ORDER + max_len);
@@ -70,52 +67,8 @@ __global__ __launch_bounds__(AR_THREADS) void ar_fill_kernel(const float* wav, c
     }
     __syncthreads();
 
-    // 2  the two fits
-    const int pmax = p[0] > p[1] ? p[0] : p[1];
-    for (int m = 0; m < pmax; ++m) {
-        double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int s = 0; s < 2; ++s) {
-            if (m >= p[s]) continue;
-            const double* F = lds + (long)s * 2 * context;
-            const double* B = F + context;
-            const long pairs = C[s] - 1 - m;
-            for (long i = tid; i < pairs; i += AR_THREADS) {
-                const double f = F[i + m + 1], bk = B[i];
-                v[3 * s] = ar_mac(v[3 * s], f, bk);
-                v[3 * s + 1] = ar_mac(v[3 * s + 1], f, f);
-                v[3 * s + 2] = ar_mac(v[3 * s + 2], bk, bk);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            const double w = wave_sum_d_dpp(v[q]);                            // every lane of every wave is here
-            if (lane == 0) red[wv * 6 + q] = w;
-        }
-        __syncthreads();
-        for (int s = 0; s < 2; ++s) {
-            if (m >= p[s]) continue;
-            const double fb = ar_sum4(red[3 * s], red[6 + 3 * s], red[12 + 3 * s], red[18 + 3 * s]);
-            const double ff = ar_sum4(red[3 * s + 1], red[6 + 3 * s + 1], red[12 + 3 * s + 1], red[18 + 3 * s + 1]);
-            const double bb = ar_sum4(red[3 * s + 2], red[6 + 3 * s + 2], red[12 + 3 * s + 2], red[18 + 3 * s + 2]);
-            const double kr = ar_reflection(fb, ff, bb);
-            const double* a_old = coef + (s * 2 + cur[s]) * AR_COEF;
-            double* a_new = coef + (s * 2 + (cur[s] ^ 1)) * AR_COEF;
-            if (tid <= m + 1) {                                               // a <- [a, 0] + k reverse([a, 0])
-                const double aj = tid <= m ? a_old[tid] : 0.0, ar = tid >= 1 ? a_old[m + 1 - tid] : 0.0;
-                a_new[tid] = ar_axpy(aj, kr, ar);
-            }
-            cur[s] ^= 1;
-            double* F = lds + (long)s * 2 * context;
-            double* B = F + context;
-            const long pairs = C[s] - 1 - m;
-            for (long i = tid; i < pairs; i += AR_THREADS) {
-                const double f = F[i + m + 1], bk = B[i];
-                F[i + m + 1] = ar_axpy(f, kr, bk);
-                B[i] = ar_axpy(bk, kr, f);
-            }
-        }
-        __syncthreads();
-    }
+    // 2  the two fits (viai_ar_fit.h)
+    ar_burg_block<2>(lds, 2L * context, (long)context, C, p, coef, red, cur);
 
     // 3  seeds (the last p context samples, read again: the fit has overwritten its arrays), then the two extrapolations
     double* P0 = lds + AR_MAX_ORDER;                                           // P[-j], j <= p: the context; P[i], i < L: the prediction
@@ -160,25 +113,6 @@ inline bool ar_args_ok(const float* wav, long stride, int B, long n, const int* 
     return wav != nullptr && count != nullptr && start != nullptr && length != nullptr && out != nullptr && filled != nullptr && B >= 1 &&
            K >= 1 && n >= 1 && n < (1L << 31) && stride >= n && out_stride >= n && (long)B * K <= 0x7fffffffL &&
            ar_limits_ok(order, context, max_len);
-}
-
-// Burg on x[0 .. C) in plain loops: a[0 .. p], p = min(order, C / 2); F and B are scratch of C doubles each
-void ar_fit_plain(const double* x, long C, int p, double* a, double* F, double* B) {
-    double a_new[AR_COEF];
-    for (long j = 0; j < C; ++j) F[j] = B[j] = x[j];
-    a[0] = 1.0;
-    for (int m = 0; m < p; ++m) {
-        double fb, ff, bb;
-        ar_dot3(F, B, C, m, &fb, &ff, &bb);
-        const double kr = ar_reflection(fb, ff, bb);
-        for (int j = 0; j <= m + 1; ++j) a_new[j] = ar_axpy(j <= m ? a[j] : 0.0, kr, j >= 1 ? a[m + 1 - j] : 0.0);
-        for (int j = 0; j <= m + 1; ++j) a[j] = a_new[j];
-        for (long i = 0; i < C - 1 - m; ++i) {
-            const double f = F[i + m + 1], bk = B[i];
-            F[i + m + 1] = ar_axpy(f, kr, bk);
-            B[i] = ar_axpy(bk, kr, f);
-        }
-    }
 }
 
 }  // namespace
