@@ -596,6 +596,53 @@ int viai_ar_fill_host(const float* wav, const int* lengths, long stride, int B, 
  * *p = min(order, C / 2).  Refuses a NULL pointer, C outside 0 .. 4096, order outside 1 .. 128.                                                */
 int viai_ar_fit_host(const float* x, int C, int order, double* a, int* p);
 
+/* ---- crackle and short gaps: Janssen's least-squares AR interpolation (csrc/janssen_fill.hip, csrc/viai_janssen_rule.h on csrc/viai_ar_rule.h;
+ * additive to ABI v20) ----
+ * viai_ar_fill treats every listed run on its own and cuts its contexts at the neighbouring runs; where runs are dense (crackle) the contexts
+ * shrink to a few samples.  Here runs that lie within `context` of each other form a CLUSTER, one all-pole model is fitted to the cluster's whole
+ * window with the current estimates in place, ALL its missing samples are solved for jointly (Janssen, Veldhuis and Vries 1986), and that is
+ * repeated `iters` times.  fp64 arithmetic of + - * / and comparisons only, each operation rounded once, every sum in a stated order: the
+ * kernel and the host mirror call the same functions of csrc/viai_janssen_rule.h and give the same bits.
+ * For row b, len = clamp(lengths[b], 0, n) (n when lengths is NULL) and listed = min(max(count[b], 0), K).  Entry k < listed is
+ * [s, e) = [start[b][k], start[b][k] + length[b][k]), L = e - s; front_k = max(0, start[b][j] + max(length[b][j], 0) over j < k) is the end of
+ * everything listed in front of it (for lists in position order: the end of entry k - 1).
+ *   USABLE    1 <= L <= max_len, s >= front_k and e <= len.  Every other entry, and every k >= listed, is SKIPPED: filled = 0, no sample written.
+ *             A skipped entry still is a wall for its neighbours' windows.
+ *   CLUSTERS  integers only.  A cluster opens at the first usable entry not yet in one.  The next entry j joins iff it is usable,
+ *             s_j - e_last < context, M + L_j <= 1024, (M + L_j) (order + 1) <= 8192 and (e_j - s_first) + 2 context <= 4096 (M: the unknowns so
+ *             far).  An entry that does not join closes the cluster; if usable it opens the next one.
+ *   WINDOW    [max(s_first - context, front_first, 0), max(min(e_last + context, start of the entry behind the last member if listed, len),
+ *             e_last)); W its size, M its unknowns at window positions t_0 < ... < t_{M-1}.  No window holds an unknown of another cluster, so
+ *             out may be wav itself.  A non-finite known sample reads as 0.0; samples outside the window count as 0.0.
+ *   ITERATE   the unknowns start at 0.0 and stay fp64 between iterations.  p = min(order, W / 2); p < 1: zeros are written, filled = 4.
+ *             iters times: a[0 .. p] = Burg's fit of viai_ar_fill (FIT and SUMS above, unchanged) on the window with the current estimates;
+ *             b_l = sum_{k = 0 .. p - l} a_k a_{k+l}; G_ij = b_{|t_i - t_j|} when |t_i - t_j| <= p, else 0; r_i = 0.0 - sum_{l = -p .. p}
+ *             b_{|l|} x0[t_i + l] over the positions inside the window, x0 the window with 0.0 at the unknowns; G = L D L^T, solve, the
+ *             unknowns <- the solution.  A pivot d_j that is not > 0.0 or not finite stops everything: the estimates of the last completed
+ *             iteration stay (zeros when none completed), filled = 5.
+ *   SUMS      b_l: ascending k from +0.0, acc = acc + a_k a_{k+l} (one rounded product, one rounded sum).  r_i: ascending l from +0.0 in the same
+ *             way (an unknown's term adds its 0.0), then 0.0 - acc.
+ *   SOLVE     inside the index band of p sub-diagonals (|t_i - t_j| >= |i - j|: G and all fill lie there), right-looking: for j = 0 .. M - 1:
+ *             d_j = A_jj; for i = j + 1 .. min(j + p, M - 1): c_i = A_ij, l_i = c_i / d_j, z_i = z_i - l_i z_j (z starts as r); then
+ *             A_ik = A_ik - l_i c_k for j < k <= i (the product is l_i c_k, not l_i d_j l_k).  So every element takes its updates one at a
+ *             time in ascending j.  Then y_i = z_i / d_i, and for j = M - 1 .. 1: x_i = x_i - l_ji x_j for i = j - 1 .. max(j - p, 0).
+ *   WRITE     out[t_i] = (float)x_i, one rounding, at the unknowns only.
+ *   filled    the same for every member of a cluster: 1 solved for all iters, 4 no model, 5 stopped at a pivot; 0 skipped or not listed.
+ * Memory as viai_ar_fill.  ONE launch, one block of 256 threads per (row, entry index): the block of a cluster's first member does the cluster
+ * and writes filled of all members, a skipped entry's block writes its 0, every other block returns at once; no atomics, no workspace, nothing
+ * synced; dynamic LDS 123 056 bytes per block whatever the arguments (the lists are read on the device, so the host cannot know W or M).
+ * Refuses with hipErrorInvalidValue before any launch: what viai_ar_fill refuses, with context outside 2 .. 1024, iters outside 1 .. 16 and
+ * max_len outside 1 .. min(1024, 8192 / (order + 1), 4096 - 2 context).                                                                      */
+int viai_janssen_fill(const float* wav, const int* lengths, long stride, int B, long n, const int* count, const int* start, const int* length,
+                      int K, int order, int context, int max_len, int iters, float* out, long out_stride, int* filled, void* stream);
+/* the same rule with plain loops from the same header, every pointer in HOST memory.  Same refusals (the alignment rule apart).                */
+int viai_janssen_fill_host(const float* wav, const int* lengths, long stride, int B, long n, const int* count, const int* start,
+                           const int* length, int K, int order, int context, int max_len, int iters, float* out, long out_stride, int* filled);
+/* USABLE, CLUSTERS and WINDOW alone, for pinning; HOST memory.  Per entry (B, K) int32: leader = the index of its cluster's first member (-1:
+ * skipped, the other three are then 0), the window [win_lo, win_hi) and the cluster's M.                                                       */
+int viai_janssen_plan_host(const int* lengths, int B, long n, const int* count, const int* start, const int* length, int K, int order,
+                           int context, int max_len, int* leader, int* win_lo, int* win_hi, int* unknowns);
+
 /* ---- clicks: impulsive damage found in a prediction residual (csrc/click_detect.hip, csrc/viai_click_rule.h; additive to ABI v20) ----
  * A click is neither silent nor clipped nor non-finite, so viai_gap_detect cannot see it.  Here an all-pole model is fitted to a stretch of the
  * signal, the signal is run through the inverse (prediction-error) filter, and a click is where the squared residual stands far above its own

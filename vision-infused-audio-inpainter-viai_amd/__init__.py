@@ -14,6 +14,8 @@ name; the top-level `viai_amd/` shim maps the import name onto it).
   wav_resample  clips at any sample rate: Resampler (polyphase, HIP), gap_at_rate, inpaint_at_rate
   gap_detect    where a clip is damaged: find_gaps (dropouts, clipping, non-finite samples; HIP), find_gaps_host, repair
   ar_fill       short gaps without a network: Burg autoregressive interpolation, ar_fill (HIP), ar_fill_host, ar_fit_host
+  janssen       dense runs (crackle) solved jointly per window: Janssen's least-squares AR interpolation, janssen_fill (HIP), janssen_fill_host,
+                janssen_plan_host
   click_detect  where a clip holds clicks: find_clicks (outliers of an AR prediction residual; HIP), find_clicks_host, declick, declick_host,
                 declick_file
   video     raw frames and flow maps -> the visual branch's blocks: motion_box, resize_u8, prepare, VideoFrontEnd (HIP), motion_box_host
@@ -41,6 +43,9 @@ def __getattr__(name):
     if name in ("ar_fill_host", "ar_fit_host"):
         from . import ar_fill
         return getattr(ar_fill, name)
+    if name in ("janssen_fill", "janssen_fill_host", "janssen_plan_host"):
+        from . import janssen
+        return getattr(janssen, name)
     if name in ("find_clicks", "find_clicks_host", "declick", "declick_host", "declick_file"):
         from . import click_detect
         return getattr(click_detect, name)

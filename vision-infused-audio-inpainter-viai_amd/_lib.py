@@ -178,6 +178,9 @@ SIGNATURES = {
     "viai_ar_fill": (_I, [_P, _P, _L, _I, _L, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P, _P]),
     "viai_ar_fill_host": (_I, [_P, _P, _L, _I, _L, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P]),
     "viai_ar_fit_host": (_I, [_P, _I, _I, _P, _IP]),
+    "viai_janssen_fill": (_I, [_P, _P, _L, _I, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
+    "viai_janssen_fill_host": (_I, [_P, _P, _L, _I, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P]),
+    "viai_janssen_plan_host": (_I, [_P, _I, _L, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "viai_click_detect_ws_bytes": (_L, [_I, _L, _I]),
     "viai_click_detect": (_I, [_P, _P, _L, _I, _L, _I, _F, _I, _I, _F, _I, _I, _I, _P, _P, _P, _P, _P]),
     "viai_click_detect_host": (_I, [_P, _P, _L, _I, _L, _I, _F, _I, _I, _F, _I, _I, _I, _P, _P, _P]),

@@ -3,6 +3,7 @@
     ar_fill        every listed gap of every row of a batch, one launch -> (out, filled)
     ar_fill_host   the same rule on numpy arrays, in plain C++ on the host (`viai_ar_fill_host`): no GPU needed
     ar_fit_host    the Burg fit alone on one numpy vector (`viai_ar_fit_host`): coefficients and order
+    janssen_fill, janssen_fill_host, janssen_plan_host   re-exported from `viai_amd.janssen`: dense runs (crackle) solved jointly per window
 
 The rule (include/viai_hip.h states it in full, csrc/viai_ar_rule.h is its arithmetic): an all-pole model is fitted to the clean samples on
 each side of a gap, extrapolated into it from both sides, and the two predictions are cross-faded.  fp64, + - * / only, every sum in a fixed
@@ -16,6 +17,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from .janssen import janssen_fill, janssen_fill_host, janssen_plan_host  # noqa: F401
 
 MAX_ORDER, MAX_CONTEXT, MAX_LEN = 128, 4096, 4096          # AR_MAX_* of csrc/viai_ar_rule.h
 

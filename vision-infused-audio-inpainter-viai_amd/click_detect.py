@@ -2,8 +2,8 @@
 
     find_clicks        impulsive damage (clicks, crackle, bit errors, a single wild sample) of every row of a batch -> Gaps(count, start, length)
     find_clicks_host   the same rule on a numpy array, in plain C++ on the host (`viai_click_detect_host`): no GPU needed
-    declick            `find_clicks` + `ar_fill`, the lists never leaving the device -> (out, gaps, filled)
-    declick_host       `find_clicks_host` + `ar_fill_host`
+    declick            `find_clicks` + `ar_fill` (or `janssen_fill`, method="janssen"), the lists never leaving the device -> (out, gaps, filled)
+    declick_host       `find_clicks_host` + `ar_fill_host` (or `janssen_fill_host`)
     declick_file       a WAV file in, a WAV file out: only the bytes of the detected runs change
 
 The rule (include/viai_hip.h states it in full, csrc/viai_click_rule.h is its arithmetic): every tile of 4096 samples gets an all-pole model by
@@ -122,32 +122,55 @@ def find_clicks_host(wav, lengths=None, order=32, k=5.0, passes=2, guard=2, floo
     return Gaps(count, start, length)
 
 
-def declick(wav, lengths=None, ar_order=32, ar_context=1024, **find_clicks_kwargs):
+def _method(what, method, ar_iters):
+    if method not in ("burg", "janssen"):
+        raise ValueError("%s: method is 'burg' or 'janssen'" % what)
+    if method == "burg" and ar_iters is not None:
+        raise ValueError("%s: ar_iters belongs to method='janssen'" % what)
+    return {} if ar_iters is None else {"iters": ar_iters}
+
+
+def declick(wav, lengths=None, ar_order=32, ar_context=1024, method="burg", ar_iters=None, **find_clicks_kwargs):
     """Find the clicks of wav (B, n) on the GPU and interpolate them: `find_clicks(wav, lengths, **find_clicks_kwargs)`, then
     `ar_fill(wav, gaps, lengths, order=ar_order, context=ar_context)` on the lists where they lie.  Returns (out, gaps, filled).
+
+    method   "burg" (the default): `ar_fill`, every run on its own.  "janssen": `janssen_fill(..., iters=ar_iters)` (default 3), runs that
+             lie within ar_context of each other solved jointly, which is what dense crackle needs; ar_context is then at most 1024, runs
+             longer than the rule allows come back with filled = 0 and are NOT handed to `ar_fill`.
 
     Nothing happens on the host in between: five launches and a clone, no synchronisation.  out is a new tensor; every sample outside the
     listed runs, and every row without a click, keeps its bits.  A row with more runs than `max_gaps` has its first max_gaps filled and says
     so in gaps.count: the caller decides (`declick_file` refuses to write)."""
-    from .ar_fill import ar_fill
+    extra = _method("declick", method, ar_iters)
     gaps = find_clicks(wav, lengths, **find_clicks_kwargs)
-    out, filled = ar_fill(wav, gaps, lengths=lengths, order=ar_order, context=ar_context)
+    if method == "janssen":
+        from .janssen import janssen_fill
+        out, filled = janssen_fill(wav, gaps, lengths=lengths, order=ar_order, context=ar_context, **extra)
+    else:
+        from .ar_fill import ar_fill
+        out, filled = ar_fill(wav, gaps, lengths=lengths, order=ar_order, context=ar_context)
     return out, gaps, filled
 
 
-def declick_host(wav, lengths=None, ar_order=32, ar_context=1024, **find_clicks_kwargs):
-    """`declick` on numpy arrays: `find_clicks_host` + `ar_fill_host`.  Needs the built library, not a GPU."""
+def declick_host(wav, lengths=None, ar_order=32, ar_context=1024, method="burg", ar_iters=None, **find_clicks_kwargs):
+    """`declick` on numpy arrays: `find_clicks_host` + `ar_fill_host` (or `janssen_fill_host`).  Needs the built library, not a GPU."""
     import numpy as np
 
-    from .ar_fill import ar_fill_host
+    extra = _method("declick_host", method, ar_iters)
     wav = np.array(np.asarray(wav, dtype=np.float32), order="C", copy=True)      # rows with their own strides, whatever view came in
     gaps = find_clicks_host(wav, lengths, **find_clicks_kwargs)
-    out, filled = ar_fill_host(wav, gaps, lengths=lengths, order=ar_order, context=ar_context)
+    if method == "janssen":
+        from .janssen import janssen_fill_host
+        out, filled = janssen_fill_host(wav, gaps, lengths=lengths, order=ar_order, context=ar_context, **extra)
+    else:
+        from .ar_fill import ar_fill_host
+        out, filled = ar_fill_host(wav, gaps, lengths=lengths, order=ar_order, context=ar_context)
     return out, gaps, filled
 
 
 def declick_file(src, dst, **kwargs):
-    """Declick the WAV file `src` into `dst`; returns (Gaps, WavInfo).  kwargs are `declick`'s.  Channels are rows of one call:
+    """Declick the WAV file `src` into `dst`; returns (Gaps, WavInfo).  kwargs are `declick`'s (method="janssen" and ar_iters among them).
+    Channels are rows of one call:
 
         1  read_wav(src, mono=False): the data chunk goes to the device once
         2  declick on the channel planes

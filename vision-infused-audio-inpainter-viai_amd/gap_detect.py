@@ -131,7 +131,7 @@ def _without_filled(count, start, length, filled):
 
 
 def repair(inpainter, wav, gaps=None, uniforms=None, fade=0, sample_rate=None, ar_below=0, ar_order=32, ar_context=1024, ar_lengths=None,
-           **find_gaps_kwargs):
+           ar_method="burg", ar_iters=None, **find_gaps_kwargs):
     """Detect the gaps of wav (B, n) and regenerate them with `inpainter` (an `AudioInpainter`).  Returns (waveform, Gaps).
 
     gaps       a `Gaps` from an earlier `find_gaps` (tensors or arrays); without it `find_gaps(wav, **find_gaps_kwargs)` runs.
@@ -147,6 +147,10 @@ def repair(inpainter, wav, gaps=None, uniforms=None, fade=0, sample_rate=None, a
                a clip whose short gaps already hold plausible signal.  When nothing remains no pass runs, `inpainter` may be None and its
                limits on rows and hops do not apply.  ar_lengths: (B,) row lengths for `ar_fill` (contexts stop there); default: the
                `lengths` the detection was given, else n.
+    ar_method  "burg" (the default): `ar_fill` as above.  "janssen": one `janssen_fill` launch instead (`viai_amd.janssen`: runs within
+               ar_context of each other solved jointly, ar_iters rounds, default 3; ar_context at most 1024), with
+               max_len = min(ar_below - 1, the rule's limit for ar_order and ar_context).  Entries that come back 0 go to the inpainter as
+               above: there is no fallback from one autoregressive method to the other.
 
     count, start and length come to the host ONCE (one synchronisation).  If any row has more gaps than the lists hold (count > K) a ValueError
     names the rows and nothing is repaired: an overflowing detection is never half repaired.  Then pass k = 0 .. max(count) - 1 calls
@@ -163,6 +167,8 @@ def repair(inpainter, wav, gaps=None, uniforms=None, fade=0, sample_rate=None, a
     B = wav.size(0)
     if int(ar_below) != ar_below or ar_below < 0:
         raise ValueError("repair: ar_below is a length in samples, 0 for no autoregressive fill")
+    if ar_method not in ("burg", "janssen") or (ar_method == "burg" and ar_iters is not None):
+        raise ValueError("repair: ar_method is 'burg' or 'janssen', and ar_iters belongs to 'janssen'")
     if gaps is None:
         gaps = find_gaps(wav, **find_gaps_kwargs)
         if ar_lengths is None:
@@ -183,9 +189,15 @@ def repair(inpainter, wav, gaps=None, uniforms=None, fade=0, sample_rate=None, a
     out = wav
     filled_any = False
     if ar_below > 1 and B > 0 and K > 0 and int(count.max()) > 0:
-        from .ar_fill import MAX_LEN, ar_fill
-        out, filled = ar_fill(wav, (count.to(torch.int32), start.to(torch.int32), length.to(torch.int32)), lengths=ar_lengths,
-                              order=ar_order, context=ar_context, max_len=min(int(ar_below) - 1, MAX_LEN))
+        lists = (count.to(torch.int32), start.to(torch.int32), length.to(torch.int32))
+        if ar_method == "janssen":
+            from .janssen import janssen_fill, rule_max_len
+            out, filled = janssen_fill(wav, lists, lengths=ar_lengths, order=ar_order, context=ar_context,
+                                       iters=3 if ar_iters is None else ar_iters,
+                                       max_len=min(int(ar_below) - 1, max(rule_max_len(ar_order, ar_context), 1)))
+        else:
+            from .ar_fill import MAX_LEN, ar_fill
+            out, filled = ar_fill(wav, lists, lengths=ar_lengths, order=ar_order, context=ar_context, max_len=min(int(ar_below) - 1, MAX_LEN))
         count, start, length = _without_filled(count, start, length, filled.cpu())
         filled_any = True
     passes = int(count.max()) if B > 0 else 0

@@ -333,9 +333,10 @@ def save_wav(wav, path, sample_rate=16000):
     write_wav(path, wav, sample_rate, "s16", normalize=True)
 
 
-def repair_file(inpainter, src, dst, max_gaps=16, ar_below=0, ar_order=32, ar_context=1024, **find_gaps_kwargs):
+def repair_file(inpainter, src, dst, max_gaps=16, ar_below=0, ar_order=32, ar_context=1024, ar_method="burg", ar_iters=None,
+                **find_gaps_kwargs):
     """Repair the WAV file `src` into `dst`; returns (Gaps, WavInfo).  Channels are rows of one `repair` call.  ar_below / ar_order /
-    ar_context go to `repair` as they are (0, the default: every gap goes to the inpainter); the autoregressive fill sees the file's own
+    ar_context / ar_method / ar_iters go to `repair` as they are (0, the default: every gap goes to the inpainter); the autoregressive fill sees the file's own
     length, so its contexts never reach into the zero padding of step 3.
 
         1  read_wav(src, mono=False); a channel count the inpainter cannot take as rows (not 1, 2, 4 or 8) raises before any work
@@ -367,7 +368,7 @@ def repair_file(inpainter, src, dst, max_gaps=16, ar_below=0, ar_order=32, ar_co
         padded = wav                                                        # at another rate inpaint_at_rate pads on the front end's grid
     if ar_below:
         out, _ = repair(inpainter, padded, gaps=gaps, sample_rate=info.sample_rate, ar_below=ar_below, ar_order=ar_order,
-                        ar_context=ar_context, ar_lengths=[n] * info.channels)
+                        ar_context=ar_context, ar_lengths=[n] * info.channels, ar_method=ar_method, ar_iters=ar_iters)
     else:
         out, _ = repair(inpainter, padded, gaps=gaps, sample_rate=info.sample_rate)
     patched = patch_pcm(data, out[:, :n], info.fmt, gaps).cpu().numpy().tobytes()
