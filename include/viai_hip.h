@@ -505,6 +505,14 @@ int viai_mel_ssim(const float* ref, const float* est, const float* mask, const d
 #define VIAI_WAV_RESAMPLE_MAX_TABLE 4194304
 /* pure arithmetic.  Refuses (hipErrorInvalidValue) rates below 1, zeros < 1, null pointers and a table over the cap.                          */
 int viai_wav_resample_geom(int sr_in, int sr_out, int zeros, int* L, int* M, int* H, int* T);
+/* the launch form viai_wav_resample takes for a plan (L, M, H); pure arithmetic, touches no device.  A tile is lt * g * pp consecutive outputs
+ * and stages span = floor((lt g pp - 1) M / L) + 2 H + 3 words of LDS (at most 16 384).
+ *   pp = 4  the period form, L <= 512: lt = L, work item w keeps q = w mod L and takes the periods w / L + g {0, 1, 2, 3} of the tile; g = 1 when
+ *           its span fits, a larger g <= max(1, 1024 / L) only where it fills the block's passes better by more than a hundredth
+ *   pp = 1  the consecutive form, L > 512 or no period tile fits: g = 1, lt = the largest of 1024, 512, 256, 128, 64 whose span fits
+ *   pp = 0  no tile fits (lt = g = span = 0): viai_wav_resample refuses the plan
+ * Returns 0 in all three cases; refuses (hipErrorInvalidValue) null pointers, L or M < 1, H < 0.                                              */
+int viai_wav_resample_form(int L, int M, int H, int* pp, int* lt, int* g, int* span);
 /* the table in HOST memory: taps L * T floats, first L ints, computed in fp64 (I0 by its power series) and rounded once to fp32.  Refuses what
  * the plan refuses, rolloff outside (0, 1] and beta outside [0, 700).                                                                         */
 int viai_wav_resample_taps(int sr_in, int sr_out, int zeros, double rolloff, double beta, float* taps, int* first);

@@ -2,7 +2,9 @@
 tests/wav_io_common.py (six formats, 1, 2, 3 and 8 channels, 1 .. 2 T + 17 frames with T = VIAI_PCM_TILE = 1024: a lone frame, the 16-byte edge,
 the tile edge, a tail tile), at other storage offsets, with nothing written outside the outputs; the normalised encode gives the reference's
 save_wav bytes of tests/golden/wav_io.npz; `patch_pcm` takes `find_gaps`'s tensors as they are; files round-trip; and `repair_file` leaves every
-byte outside the detected gaps' samples as it was.  No tolerance anywhere.  The largest clip is 2 T + 17 = 2065 frames."""
+byte outside the detected gaps' samples as it was; `repair(sample_rate=)` and `repair_file` at 11 025 and 44 100 Hz, through `inpaint_at_rate`, are
+the composition written out pass by pass, bit for bit.  No tolerance anywhere.  The largest clip of the table is 2 T + 17 = 2065 frames, the
+largest of the foreign-rate tests 9000."""
 import os
 import types
 
@@ -201,8 +203,9 @@ class StubInpainter:
         return out
 
 
-def damaged_file(fmt, channels, n, gaps, rate=RATE):
-    """(file bytes, data bytes): nonzero samples with exact zeros in the gaps, a LIST chunk in front of the data and a chunk behind it"""
+def damaged_file(fmt, channels, n, gaps, rate=RATE, tail=b""):
+    """(file bytes, data bytes): nonzero samples with exact zeros in the gaps, a LIST chunk in front of the data and a chunk behind it; `tail`:
+    the bytes of a partial frame at the end of the data chunk"""
     rng = np.random.RandomState(n + channels)
     wav = (rng.randint(100, 30000, (channels, n)) * rng.choice([-1, 1], (channels, n))).astype(f32) / f32(32768)
     for c, runs in enumerate(gaps):
@@ -210,7 +213,7 @@ def damaged_file(fmt, channels, n, gaps, rate=RATE):
             wav[c, s:e] = 0
     data = W.encode_rule(wav, fmt).tobytes()
     before, after = W.chunk(b"LIST", b"INFOISFT\x03\x00\x00\x00abc\x00"), W.chunk(b"note", b"kept")
-    return W.wav_file(fmt, channels, rate, data, extra_before=before, extra_after=after), data
+    return W.wav_file(fmt, channels, rate, data + tail, extra_before=before, extra_after=after), data
 
 
 @pytest.mark.parametrize("fmt,channels", (("s16", 2), ("s24", 1)))
@@ -282,3 +285,120 @@ def test_repair_at_the_front_ends_rate_is_the_direct_call():
     out_b, gaps_b = repair(b, wav, sample_rate=RATE)
     assert a.calls == b.calls and len(a.calls) == 1 and torch.equal(out_a, out_b)
     assert all(torch.equal(x, y) for x, y in zip(gaps_a, gaps_b))
+
+
+# ----------------------------------------------------------------------------- 5. files and clips at another rate than the front end's
+# 11 025 Hz: the down leg (11 025 -> 16 000, L = 640) takes the resampler's consecutive form and the up leg (L = 441) its period form;
+# 44 100 Hz: the period form both ways.  n is chosen so that the low-rate clip is no whole number of hops.
+FOREIGN = {11025: 4000, 44100: 9000}
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def runs_of(n, channels=2):
+    """row 0 holds three runs, the last one up to the clip's end; row 1 holds one, so its later passes see length 0"""
+    return [[(300, 400), (1500, 1570), (n - 150, n)], [(700, 820)]][:channels]
+
+
+def composition(wav, rate, count, start, length):
+    """`repair(stub, wav, gaps=, sample_rate=rate)` written out from the public pieces, pass by pass: down to whole hops, the gap widened, the
+    stub, up over the run only into a clone.  Returns (the result after every pass, the stub's calls)."""
+    from viai_amd.wav_resample import Resampler, gap_at_rate
+    down, up = Resampler(rate, RATE), Resampler(RATE, rate)
+    stub = StubInpainter()
+    n = wav.size(1)
+    m = -(-down.out_len(n) // HOP) * HOP
+    assert down.out_len(n) % HOP != 0
+    steps = [wav.float().clone()]
+    for k in range(int(max(count))):
+        gs = [int(start[b][k]) if k < int(count[b]) else 0 for b in range(len(count))]
+        gl = [int(length[b][k]) if k < int(count[b]) else 0 for b in range(len(count))]
+        low = down(steps[-1], out_len=m)
+        low_start, low_len = gap_at_rate(gs, gl, down, m)
+        low_out = stub(low, low_start, low_len)
+        nxt = steps[-1].clone()
+        up(low_out, out=nxt, window=(gs, [s + l for s, l in zip(gs, gl)]), out_len=n)
+        steps.append(nxt)
+    return steps[1:], stub.calls
+
+
+@pytest.mark.parametrize("rate", sorted(FOREIGN))
+def test_repair_at_another_rate_is_the_composition_pass_by_pass(rate):
+    from viai_amd.gap_detect import Gaps, repair
+    from viai_amd.wav_resample import Resampler
+    n, K = FOREIGN[rate], 4
+    assert Resampler(rate, RATE).launch_form()[0] == (1 if rate == 11025 else 4) and Resampler(RATE, rate).launch_form()[0] == 4
+    runs = runs_of(n)
+    wav = torch.rand(2, n, generator=torch.Generator().manual_seed(rate)) * 0.8 + 0.1
+    count = torch.tensor([len(r) for r in runs], dtype=torch.int32)
+    start, length = torch.zeros(2, K, dtype=torch.int32), torch.zeros(2, K, dtype=torch.int32)
+    inside = torch.zeros(2, n, dtype=torch.bool)
+    for b, row in enumerate(runs):
+        for k, (s, e) in enumerate(row):
+            wav[b, s:e] = 0
+            start[b, k], length[b, k] = s, e - s
+            inside[b, s:e] = True
+    wav, inside = wav.cuda(), inside.cuda()
+    before = wav.clone()
+    stub = StubInpainter()
+    out, gaps = repair(stub, wav, gaps=Gaps(count.cuda(), start.cuda(), length.cuda()), sample_rate=rate)
+    steps, calls = composition(wav, rate, count, start, length)
+    m = -(-Resampler(rate, RATE).out_len(n) // HOP) * HOP
+    assert tuple(out.shape) == (2, n) and torch.equal(bits(wav), bits(before))
+    assert len(stub.calls) == 3 and stub.calls == calls and all(c[0] == (2, m) for c in calls)
+    assert [c[2][1] for c in calls][1:] == [0, 0] and all(c[2][0] > 0 for c in calls) and calls[0][2][1] > 0
+    assert torch.equal(bits(out), bits(steps[-1]))                        # bit for bit the composition
+    assert torch.equal(bits(out)[~inside], bits(wav)[~inside])            # every sample outside the listed runs keeps the input's bits
+    for b, row in enumerate(runs):
+        for s, e in row:
+            assert int((out[b, s:e] != 0).sum()) > (e - s) // 2, (b, s)   # and the runs were written
+    # a pass with length 0 changes nothing in its row: row 1 after passes 2 and 3 is row 1 after pass 1, in the composition and in repair()
+    assert torch.equal(bits(steps[1][1]), bits(steps[0][1])) and torch.equal(bits(steps[2][1]), bits(steps[0][1]))
+    one, _ = repair(StubInpainter(), wav, gaps=Gaps(count.clamp(max=1), start[:, :1], length[:, :1]), sample_rate=rate)
+    assert torch.equal(bits(one), bits(steps[0])) and torch.equal(bits(one[1]), bits(out[1]))
+
+
+@pytest.mark.parametrize("fmt,channels,rate", (("s16", 2, 11025), ("s24", 1, 11025), ("s16", 2, 44100)))
+def test_repair_file_at_another_rate_is_the_composition_and_keeps_every_other_byte(fmt, channels, rate, tmp_path):
+    from viai_amd import wav_io as wio
+    from viai_amd.gap_detect import find_gaps_host
+    n = FOREIGN[rate]
+    runs = runs_of(n, channels)
+    tail = b"\x07\x08"                                                    # a partial frame behind the last whole one
+    buf, data = damaged_file(fmt, channels, n, runs, rate=rate, tail=tail)
+    src, dst = str(tmp_path / "src.wav"), str(tmp_path / "dst.wav")
+    open(src, "wb").write(buf)
+    stub = StubInpainter()
+    got_gaps, info = wio.repair_file(stub, src, dst)
+    bps, off = W.BYTES[fmt], info.data_offset
+    assert info == wio.parse_wav(buf) and info[:4] == (rate, channels, fmt, n) and info.data_bytes == n * channels * bps == len(data)
+    # detection ran on the clip at its own length and rate: the runs as they lie in the file, the last one ending at sample n, nothing beyond
+    decoded = wio.decode_pcm_host(np.frombuffer(data, dtype=np.uint8), fmt, channels)
+    want_gaps = find_gaps_host(decoded)
+    for g, w in zip(got_gaps, want_gaps):
+        assert g.is_cuda and np.array_equal(g.cpu().numpy(), w)
+    assert want_gaps.count.tolist() == [len(r) for r in runs]
+    for c, row in enumerate(runs):
+        assert [(int(want_gaps.start[c, k]), int(want_gaps.start[c, k] + want_gaps.length[c, k])) for k in range(len(row))] == row
+    assert int((want_gaps.start + want_gaps.length).max()) == n
+    # the composition on the decoded clip: the same calls of the stub, on whole hops of the front end's grid
+    steps, calls = composition(dev(decoded), rate, want_gaps.count, want_gaps.start, want_gaps.length)
+    assert stub.calls == calls and len(calls) == max(len(r) for r in runs)
+    assert all(c[0][0] == channels and c[0][1] % HOP == 0 for c in calls)
+    out = open(dst, "rb").read()
+    assert len(out) == len(buf)
+    end = off + info.data_bytes
+    assert out[:off] == buf[:off] and out[end:] == buf[end:]              # header, the LIST chunk, the partial frame and the chunk behind it
+    assert buf[end:end + len(tail)] == tail and b"note" in buf[end:] and b"LIST" in buf[:off]
+    got = np.frombuffer(out, dtype=np.uint8, count=info.data_bytes, offset=off).reshape(n, channels, bps)
+    old = np.frombuffer(data, dtype=np.uint8).reshape(n, channels, bps)
+    inside = np.zeros((n, channels), dtype=bool)
+    for c, row in enumerate(runs):
+        for s, e in row:
+            inside[s:e, c] = True
+    assert np.array_equal(got[~inside], old[~inside])                     # every byte outside the detected runs' samples
+    want = wio.encode_pcm_host(steps[-1].cpu().numpy(), fmt).reshape(n, channels, bps)
+    assert np.array_equal(got[inside], want[inside])
+    assert inside[n - 1].any() and (got[inside] != old[inside]).any()

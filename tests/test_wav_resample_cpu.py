@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PL = C.POINTER(C.c_long)
 PI = C.POINTER(C.c_int)
 NEW = {"viai_wav_resample_geom": (C.c_int, 7), "viai_wav_resample_taps": (C.c_int, 7), "viai_wav_resample_out_len": (C.c_long, 3),
-       "viai_gap_at_rate": (C.c_int, 8), "viai_wav_resample": (C.c_int, 16)}
+       "viai_gap_at_rate": (C.c_int, 8), "viai_wav_resample": (C.c_int, 16), "viai_wav_resample_form": (C.c_int, 7)}
 INVAL = 1                                                                # hipErrorInvalidValue
 _TABLES = {}
 
@@ -36,7 +36,7 @@ def geom(lib, sr_in, sr_out, zeros=24):
 def lib_table(lib, sr_in, sr_out):
     """the library's table as ((L, T) float32 in period order, first), computed once per ratio"""
     if (sr_in, sr_out) not in _TABLES:
-        L, M, H, T = R.RATIOS[(sr_in, sr_out)]
+        L, M, H, T = R.plan(sr_in, sr_out)
         taps = np.zeros((T, L), dtype=np.float32)
         first = np.zeros(L, dtype=np.int32)
         assert lib.viai_wav_resample_taps(sr_in, sr_out, 24, 0.945, 8.6, taps.ctypes.data, first.ctypes.data) == 0
@@ -82,6 +82,156 @@ def test_output_length(lib):
         assert f(top, L, M) <= 2 ** 31 - 1 < f(top + 1, L, M)
         assert f(0, L, M) == 0 and f(-1, L, M) == 0
     assert f(5, 0, 1) == 0 and f(5, 1, 0) == 0
+
+
+def form(lib, L, M, H):
+    v = [C.c_int(-7) for _ in range(4)]
+    err = lib.viai_wav_resample_form(L, M, H, *[C.byref(x) for x in v])
+    return err, tuple(x.value for x in v)
+
+
+def kind(L, f):
+    """which of the eight answers of the rule a form is"""
+    return (f[0], f[1] if f[0] == 1 else 0, L <= R.PERIOD_MAX_L if f[0] == 0 else None)
+
+
+KINDS = {(4, 0, None)} | {(1, lt, None) for lt in (1024, 512, 256, 128, 64)} | {(0, 0, True), (0, 0, False)}
+
+
+def test_every_launch_form_has_a_named_plan_that_takes_it(lib):
+    """the library's answer (`viai_wav_resample_form`), the restatement `R.pick` and the table of wav_resample_common.py agree plan by plan, and
+    the named plans between them take every form the rule can return"""
+    from viai_amd import wav_resample as WR
+    named = dict(R.PERIOD_FORMS)
+    named.update({rates: f for rates, (_, f) in R.FORMS.items()})
+    named.update({rates: (0, 0, 0, 0) for rates in R.REFUSED})
+    plans = dict(R.RATIOS)
+    plans.update({rates: p for rates, (p, _) in R.FORMS.items()})
+    plans.update(R.REFUSED)
+    seen = set()
+    for rates, want in named.items():
+        L, M, H, T = plans[rates]
+        assert geom(lib, *rates) == (0, (L, M, H, T)) and R.plan(*rates) == (L, M, H, T), rates
+        assert L * T <= R.MAX_TABLE
+        assert form(lib, L, M, H) == (0, want), rates
+        assert R.pick(L, M, H) == want, rates
+        assert WR.Resampler(*rates).launch_form() == want                # the table is not built for this
+        pp, lt, g, words = want
+        if pp:
+            assert words == R.span(lt * g * pp, L, M, H) <= R.MAX_SPAN and (g == 1 if pp == 1 else lt == L)
+        seen.add(kind(L, want))
+    assert seen == KINDS
+    # each named plan is named for something: the consecutive form above the period limit and below it, the budget's edge, one item per block
+    assert R.FORMS[(11025, 16000)][0][0] > R.PERIOD_MAX_L >= R.FORMS[(4001, 400)][0][0] and R.FORMS[(4001, 400)][1][0] == 1
+    assert R.span(4 * 400, 400, 4001, 241) > R.MAX_SPAN                  # why 4001 -> 400 falls through: g = 1 of the period form does not fit
+    assert R.MAX_SPAN - 32 < R.FORMS[(28135, 521)][1][3] <= R.MAX_SPAN
+    assert R.FORMS[(300, 1)][1][:3] == (4, 1, 1) and 4 * R.FORMS[(300, 1)][1][3] > 60000
+    assert R.REFUSED[(330, 1)][0] <= R.PERIOD_MAX_L < R.REFUSED[(77109, 521)][0]
+    # refused like the plan's other queries
+    none = C.cast(None, PI)
+    assert lib.viai_wav_resample_form(160, 441, 67, none, none, none, none) == INVAL
+    for bad in ((0, 441, 67), (160, 0, 67), (160, 441, -1), (-3, 441, 67)):
+        assert form(lib, *bad)[0] == INVAL, bad
+    assert form(lib, 2, 1, 0) == (0, R.pick(2, 1, 0))                    # H = 0 is a plan the launch takes too
+
+
+def test_the_restated_rule_is_the_librarys_over_random_plans(lib):
+    """a few hundred (sr_in, sr_out, zeros), drawn so that every answer of the rule turns up, refused plans included"""
+    rng = np.random.default_rng(2024)
+    seen, checked, no_plan = set(), 0, 0
+    draws = []
+    for _ in range(120):                                                  # everyday rates both ways: short periods, small M / L
+        a, b = rng.choice([8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 96000], 2, replace=False)
+        draws.append((int(a), int(b), int(rng.integers(1, 65))))
+    for _ in range(160):                                                  # coprime-ish pairs: long periods
+        draws.append((int(rng.integers(1, 40000)), int(rng.integers(1, 40000)), int(rng.integers(1, 33))))
+    for _ in range(200):                                                  # steep decimation: M / L from 2 to 400, where the span decides
+        L = int(rng.choice([1, 2, 3, 7, 100, 400, 512, 513, 521, 1000]))
+        draws.append((L * int(rng.integers(2, 400)) + int(rng.integers(0, L + 1)), L, int(rng.integers(1, 49))))
+    for sr_in, sr_out, zeros in draws:
+        err, got = geom(lib, sr_in, sr_out, zeros)
+        L, M, H, T = R.plan(sr_in, sr_out, zeros)
+        if err != 0:
+            assert err == INVAL and L * T > R.MAX_TABLE, (sr_in, sr_out, zeros)
+            no_plan += 1
+            continue
+        assert got == (L, M, H, T) and L * T <= R.MAX_TABLE
+        want = R.pick(L, M, H)
+        assert form(lib, L, M, H) == (0, want), (sr_in, sr_out, zeros)
+        # the launch itself refuses exactly the plans without a form, before anything is launched (the pointers are never followed)
+        refused = lib.viai_wav_resample(16, None, 16, 16, 16, None, None, 1, 100, 100, 1, L, M, H, T, None) if want[0] == 0 else INVAL
+        assert refused == INVAL
+        seen.add(kind(L, want))
+        checked += 1
+    assert seen == KINDS and checked >= 300 and no_plan > 0
+    print("random plans: %d checked, %d over the table cap" % (checked, no_plan))
+
+
+def new_plans():
+    return list(R.FORMS) + [(330, 1), (77109, 521)]
+
+
+@pytest.mark.parametrize("rates", new_plans())
+def test_taps_of_the_new_plans_are_the_restatement_rounded_once(lib, rates):
+    """what test_taps_are_the_restatement_rounded_once asserts of the six, of every plan of FORMS and of two refused ones (their tables exist)"""
+    L, M, H, T = R.plan(*rates)
+    got, first = lib_table(lib, *rates)
+    want, want_first = R.table(*rates)
+    assert got.shape == (L, T) == want.shape
+    assert np.array_equal(first, want_first)
+    rounded = want.astype(np.float32)
+    ulp = np.spacing(np.abs(rounded))
+    assert np.all(np.abs(got.astype(np.float64) - rounded.astype(np.float64)) <= ulp.astype(np.float64))
+    assert np.array_equal(got == 0, rounded == 0)
+    sums = got.astype(np.float64).sum(1)
+    print("%s: largest |row sum - 1| %.3g" % (rates, float(np.abs(sums - 1).max())))
+    assert np.abs(sums - 1).max() < 3e-5
+    assert np.all(got[:, 0] == 0)
+
+
+@pytest.mark.parametrize("rates", list(R.FORMS))
+def test_the_fp32_chain_stays_inside_the_bound_for_the_new_plans(lib, rates):
+    """test_the_fp32_chain_stays_inside_the_dot_product_bound at the new plans' T (up to 14 401 terms) and the GPU test's sizes"""
+    L, M, H, T = R.plan(*rates)
+    h = lib_table(lib, *rates)[0].astype(np.float64)
+    n, m = R.value_size(rates)
+    x = np.random.default_rng(L + M).uniform(-1, 1, n).astype(np.float32)
+    want, mags = R.resample(x, L, M, H, h)
+    got, _ = R.resample(x, L, M, H, h, dtype=np.float32)
+    bound = (T + 4) * 2.0 ** -24 * mags
+    assert want.shape == (m,) and np.all(np.abs(got - want) <= bound)
+    print("%s: n = %d, m = %d, fp32 chain: largest error over the bound %.3f" % (rates, n, m, float((np.abs(got - want) / bound).max())))
+
+
+@pytest.mark.parametrize("rates", [(11025, 16000), (4001, 400), (8337, 521)])
+def test_gap_at_rate_against_brute_force_for_consecutive_form_plans(lib, rates):
+    """test_gap_at_rate_against_brute_force for plans that take the consecutive form: up, and down with filters of 483 and 771 taps"""
+    L, M, H, T = R.plan(*rates)
+    h = lib_table(lib, *rates)[0].astype(np.float64)
+    n = 2000
+    m = R.out_len(n, L, M)
+    rng = np.random.default_rng(5)
+    x = rng.uniform(-1, 1, n)
+    y = R.resample(x, L, M, H, h)[0]
+    k0, k1 = C.c_long(-7), C.c_long(-7)
+    for g0, g1 in ((0, 100), (0, 1), (900, 1100), (1000, 1001), (1900, 2000), (1999, 2000), (700, 700), (800, 790)):
+        assert lib.viai_gap_at_rate(g0, g1, L, M, H, m, C.byref(k0), C.byref(k1)) == 0
+        a, b = k0.value, k1.value
+        assert (a, b) == R.gap_at_rate(g0, g1, L, M, H, m), (g0, g1)
+        if g1 <= g0:
+            assert (a, b) == (0, 0)
+            continue
+        other = x.copy()
+        other[g0:g1] = rng.uniform(-1, 1, g1 - g0) + 2.0
+        d = R.resample(other, L, M, H, h)[0] - y
+        assert np.all(d[:a] == 0) and np.all(d[b:] == 0), (g0, g1)
+        assert 0 <= a < b <= m
+        lo, hi = R.support(a, L, M, H)
+        assert a == 0 or (hi >= g0 and lo < g1)
+        assert a == 0 or R.support(a - 1, L, M, H)[1] < g0
+        lo, hi = R.support(b - 1, L, M, H)
+        assert b == m or (hi >= g0 and lo < g1)
+        assert b == m or R.support(b, L, M, H)[0] >= g1
 
 
 def test_taps_are_the_restatement_rounded_once(lib):

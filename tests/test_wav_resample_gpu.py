@@ -375,3 +375,106 @@ def test_the_front_ends_own_rate_calls_the_inpainter_directly():
     wav = O.cf_uniform("war.wav.16", (2, N_LOW), -0.9, 0.9).contiguous().cuda()
     u = draws("mol", 2, RF + 300)
     assert torch.equal(bits(inpaint_at_rate(inp, wav, 16000, [1000, 0], [300, 0], uniforms=u)), bits(inp(wav, [1000, 0], [300, 0], uniforms=u)))
+
+
+# ----------------------------------------------------------------------------- 7. the launch forms the six ratios do not reach
+# R.FORMS: the consecutive form (wav_resample_kernel<1>) at tiles of 1024, 512, 256, 128 and 64 outputs, above the period limit and below it, a
+# span 17 words under the LDS budget, and the period form with a single work item per block.  Each test first asks the library which form the
+# plan takes, so a later change of the rule cannot move these cases onto another kernel unnoticed.  Sizes: R.value_size, a little over two tiles.
+def tile_of(rs):
+    pp, lt, g, _ = rs.launch_form()
+    return pp * lt * g
+
+
+@pytest.mark.parametrize("rates", list(R.FORMS))
+def test_values_of_the_other_launch_forms(rates):
+    """test_values_against_the_restatement for every plan of R.FORMS: rows of 1, T - 3 and n samples and a row of ones, NaN behind every length
+    in a view of wider rows, the same bound, and the DC check on the row of ones"""
+    rs, _ = resampler(rates)
+    assert ((rs.L, rs.M, rs.H, rs.T), rs.launch_form()) == R.FORMS[rates]
+    n, m = R.value_size(rates)
+    tile = tile_of(rs)
+    assert n >= 2 * rs.T + 5 and 2 * tile < m == rs.out_len(n) and m % tile != 0       # more than two tiles and a ragged one
+    lengths = [1, rs.T - 3, n, n]
+    rng = np.random.default_rng(rs.L * 1000 + rs.M)
+    buf = np.full((4, n + 13), np.nan, dtype=np.float32)
+    clips = []
+    for b, ln in enumerate(lengths):
+        clips.append(np.ones(ln, dtype=np.float32) if b == 3 else rng.uniform(-1, 1, ln).astype(np.float32))
+        buf[b, :ln] = clips[b]
+    dev = torch.from_numpy(buf).cuda()
+    wav = dev[:, :n]
+    assert wav.stride(0) == n + 13
+    y = rs(wav, lengths=lengths)
+    assert tuple(y.shape) == (4, m) and y.dtype == torch.float32
+    worst = max(check_values(rates, y[b], clips[b], m) for b in range(4))
+    k = np.arange(m)
+    i0 = k * rs.M // rs.L
+    inner = (i0 - rs.H >= 0) & (i0 + rs.H < n)
+    dc = np.abs(y[3].cpu().numpy().astype(np.float64) - 1)
+    assert inner.sum() > 0 and np.all(dc[inner] <= 3e-5 + (rs.T + 4) * 2.0 ** -24 * reference(rates, clips[3], m)[1][inner])
+    print("%s %s: n = %d, m = %d, largest error over its bound %.3f" % (rates, rs.launch_form(), n, m, worst))
+
+
+@pytest.mark.parametrize("rates", [(11025, 16000), (4001, 400), (8337, 521), (62521, 521), (300, 1)])
+def test_bits_of_the_other_launch_forms(rates):
+    """tiles of 1024 (above and below the period limit), 512 and 64 consecutive outputs and the period tile of four: a row alone and in a batch,
+    a repeat, a window that starts and ends inside tiles, and outputs asked for beyond the clip's, all bit for bit"""
+    rs, _ = resampler(rates)
+    assert rs.launch_form() == R.FORMS[rates][1]
+    tile = tile_of(rs)
+    n, m = R.value_size(rates)
+    x = (torch.rand(3, n, generator=torch.Generator().manual_seed(n)) * 2 - 1).cuda()
+    batch = rs(x)
+    assert tuple(batch.shape) == (3, m)
+    assert torch.equal(bits(rs(x)), bits(batch))
+    for b in (0, 2):
+        assert torch.equal(bits(rs(x[b:b + 1])), bits(batch[b:b + 1])), b
+    # windows: from inside tile 0 to inside tile 1; one output on each side of the edge between tiles 1 and 2; empty
+    a, e = tile - max(1, tile // 3), tile + max(2, tile // 2)
+    assert 0 < a < tile < e < 2 * tile and a % tile != 0 and e % tile != 0 and 2 * tile + 1 <= m
+    windows = [(a, e), (2 * tile - 1, 2 * tile + 1), (a, a)]
+    out = sentinel(3, m + 3)
+    got = rs(x, out=out, window=([w[0] for w in windows], [w[1] for w in windows]))
+    assert got.data_ptr() == out.data_ptr() and tuple(got.shape) == (3, m)
+    for b, (w0, w1) in enumerate(windows):
+        inside = torch.zeros(m + 3, dtype=torch.bool, device="cuda")
+        inside[w0:w1] = True
+        assert int(inside.sum()) == w1 - w0
+        assert torch.equal(bits(out[b])[:m][inside[:m]], bits(batch[b])[inside[:m]]), b
+        assert bool((bits(out[b])[~inside] == SENTINEL).all()), b
+    # more outputs than the clip has: the same bits in front, the formula on the zero-extended clip behind, exact zeros past the filter
+    quiet = R.out_len(n + rs.H, rs.L, rs.M)
+    more = quiet + tile // 2 + 3
+    padded = rs(x, out_len=more)
+    assert tuple(padded.shape) == (3, more) and m <= quiet < more
+    assert torch.equal(bits(padded[:, :m]), bits(batch))
+    assert bool((bits(padded[:, quiet:]) == 0).all())
+    check_values(rates, padded[0], x[0].cpu().numpy(), more)
+
+
+@pytest.mark.parametrize("rates", [(330, 1), (77109, 521)])
+def test_a_plan_no_tile_fits_is_refused_and_leaves_nothing_behind(rates):
+    """L <= 512 and L > 512: the plan and its table exist, the call raises before any launch, `out` keeps its bits and the next call works"""
+    from viai_amd._lib import ViaiLibraryError
+    from viai_amd.wav_resample import Resampler
+    rs = Resampler(*rates)
+    assert (rs.L, rs.M, rs.H, rs.T) == R.REFUSED[rates] and rs.launch_form() == (0, 0, 0, 0)
+    taps, first = rs.host_table()
+    assert tuple(taps.shape) == (rs.T, rs.L) and bool(torch.isfinite(taps).all()) and abs(float(taps.double().sum()) / rs.L - 1) < 3e-5
+    n = 2 * rs.M + 5
+    x = (torch.rand(2, n, generator=torch.Generator().manual_seed(n)) * 2 - 1).cuda()
+    out = sentinel(2, rs.out_len(n) + 3)
+    with pytest.raises(ViaiLibraryError, match="viai_wav_resample failed with hipError_t 1"):
+        rs(x, out=out)
+    with pytest.raises(ViaiLibraryError, match="viai_wav_resample failed with hipError_t 1"):
+        rs(x, out=out, window=(0, 1))
+    with pytest.raises(ViaiLibraryError, match="viai_wav_resample failed with hipError_t 1"):
+        rs(x)
+    torch.cuda.synchronize()                                             # nothing was launched and no error is pending
+    assert bool((bits(out) == SENTINEL).all())
+    ok = (300, 1)
+    y = resampler(ok)[0](x[:, :3000])
+    torch.cuda.synchronize()
+    for b in range(2):
+        check_values(ok, y[b], x[b, :3000].cpu().numpy())

@@ -13,12 +13,70 @@ RATIOS = {(44100, 16000): (160, 441, 67, 135), (16000, 44100): (441, 160, 24, 49
           (16000, 48000): (3, 1, 24, 49), (22050, 16000): (320, 441, 34, 69), (16000, 22050): (441, 320, 24, 49)}
 ZEROS, ROLLOFF, BETA = 24, 0.945, 8.6
 
+# The launch forms RATIOS does not reach (all six are the period form, pp = 4, with spans of at most 5426 words): rates -> ((L, M, H, T),
+# (pp, lt, g, span)) as `pick` below states the rule.  Kept apart from RATIOS: the tests that iterate over RATIOS use sizes that would be slow here.
+FORMS = {
+    (11025, 16000): ((640, 441, 24, 49), (1, 1024, 1, 755)),             # L > 512: the consecutive form, up
+    (11025, 48000): ((640, 147, 24, 49), (1, 1024, 1, 285)),
+    (16001, 16000): ((16000, 16001, 25, 51), (1, 1024, 1, 1076)),        # a period far longer than a tile
+    (4001, 400): ((400, 4001, 241, 483), (1, 1024, 1, 10717)),           # L <= 512, but one period of four outputs per item does not fit
+    (8337, 521): ((521, 8337, 385, 771), (1, 512, 1, 8949)),             # shorter consecutive tiles as M / L grows
+    (28135, 521): ((521, 28135, 1297, 2595), (1, 256, 1, 16367)),        # 17 words under the budget: 65 468 bytes of LDS
+    (36471, 521): ((521, 36471, 1681, 3363), (1, 128, 1, 12255)),
+    (62521, 521): ((521, 62521, 2881, 5763), (1, 64, 1, 13325)),
+    (300, 1): ((1, 300, 7200, 14401), (4, 1, 1, 15303)),                 # the period form with one work item per block, 61 KB of LDS
+}
+REFUSED = {(330, 1): (1, 330, 7920, 15841), (44100, 100): (1, 441, 10584, 21169),      # a valid table and no tile that fits: L <= 512 ...
+           (77109, 521): (521, 77109, 3553, 7107)}                                     # ... and L > 512
+PERIOD_FORMS = {(44100, 16000): (4, 160, 3, 5426), (16000, 44100): (4, 441, 1, 690), (48000, 16000): (4, 1, 254, 3192),
+                (16000, 48000): (4, 3, 85, 390), (22050, 16000): (4, 320, 3, 5361), (16000, 22050): (4, 441, 1, 1330)}
+
 
 def plan(sr_in, sr_out, zeros=ZEROS):
     g = math.gcd(sr_in, sr_out)
     L, M = sr_out // g, sr_in // g
     H = -(-zeros * M // L) if M > L else zeros                           # ceil(zeros / min(1, L / M)), in integers
     return L, M, H, 2 * H + 1
+
+
+THREADS, PP, MAX_SPAN, PERIOD_MAX_L, MAX_TABLE = 256, 4, 16384, 512, 1 << 22
+
+
+def span(tile_len, L, M, H):
+    """the input samples a tile of tile_len consecutive outputs stages: i0 moves by at most floor((tile_len - 1) M / L) + 1 inside it"""
+    return (tile_len - 1) * M // L + 2 * H + 3
+
+
+def pick(L, M, H):
+    """(pp, lt, g, span): the launch form of a plan, the rule of csrc/wav_resample.hip restated.  A tile is lt g pp consecutive outputs.
+    pp = 4, lt = L: the period form for L <= 512, g = 1 when its span fits and a larger g <= max(1, 1024 // L) only where L g fills passes of
+    256 lanes better by more than a hundredth; pp = 1, g = 1: the consecutive form, the largest lt of 1024 .. 64 whose span fits; (0, 0, 0, 0):
+    no tile fits the 16 384 words."""
+    if L <= PERIOD_MAX_L:
+        best, full = None, None
+        for g in range(1, max(1, 1024 // L) + 1):
+            items = L * g
+            words = span(items * PP, L, M, H)
+            if words > MAX_SPAN:
+                break
+            slots = -(-items // THREADS) * THREADS
+            if g == 1 or items * full[1] * 100 > full[0] * slots * 101:
+                best, full = (PP, L, g, words), (items, slots)
+        if best is not None:
+            return best
+    for lt in (1024, 512, 256, 128, 64):
+        if span(lt, L, M, H) <= MAX_SPAN:
+            return 1, lt, 1, span(lt, L, M, H)
+    return 0, 0, 0, 0
+
+
+def value_size(rates):
+    """(n, m) for a value test of a plan of FORMS: a little over two tiles of the plan's own tile and a ragged tail, at most a few thousand
+    outputs, and a clip long enough to hold whole filters (2 T + 5 samples)"""
+    (L, M, H, T), (pp, lt, g, _) = FORMS[rates]
+    tile = pp * lt * g
+    n = max((2 * tile + tile // 3 + 2) * M // L, 2 * T + 5)
+    return n, out_len(n, L, M)
 
 
 def out_len(n, L, M):

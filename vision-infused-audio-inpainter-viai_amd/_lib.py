@@ -168,6 +168,7 @@ SIGNATURES = {
     "viai_mel_frame_stats": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P]),
     "viai_mel_ssim": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _P]),
     "viai_wav_resample_geom": (_I, [_I, _I, _I, _IP, _IP, _IP, _IP]),
+    "viai_wav_resample_form": (_I, [_I, _I, _I, _IP, _IP, _IP, _IP]),
     "viai_wav_resample_taps": (_I, [_I, _I, _I, _D, _D, _P, _P]),
     "viai_wav_resample_out_len": (_L, [_L, _I, _I]),
     "viai_gap_at_rate": (_I, [_L, _L, _I, _I, _I, _L, C.POINTER(C.c_long), C.POINTER(C.c_long)]),

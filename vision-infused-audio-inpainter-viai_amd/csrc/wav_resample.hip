@@ -169,6 +169,16 @@ extern "C" int viai_wav_resample_geom(int sr_in, int sr_out, int zeros, int* L, 
     return wr_geom(sr_in, sr_out, zeros, L, M, H, T) ? 0 : (int)hipErrorInvalidValue;
 }
 
+extern "C" int viai_wav_resample_form(int L, int M, int H, int* pp, int* lt, int* g, int* span) {
+    if (pp == nullptr || lt == nullptr || g == nullptr || span == nullptr || L < 1 || M < 1 || H < 0) return (int)hipErrorInvalidValue;
+    const wr_launch f = wr_pick(L, M, H);
+    *pp = f.pp;
+    *lt = f.lt;
+    *g = f.g;
+    *span = (int)f.span;                                                 // at most WR_MAX_SPAN, 0 with pp = 0
+    return 0;
+}
+
 extern "C" int viai_wav_resample_taps(int sr_in, int sr_out, int zeros, double rolloff, double beta, float* taps, int* first) {
     int L, M, H, T;
     if (taps == nullptr || first == nullptr || !wr_geom(sr_in, sr_out, zeros, &L, &M, &H, &T) || !(rolloff > 0.0) || !(rolloff <= 1.0) ||

@@ -76,6 +76,14 @@ class Resampler:
         """ceil(n L / M): the outputs of n input samples"""
         return int(_lib.load().viai_wav_resample_out_len(int(n), self.L, self.M))
 
+    def launch_form(self):
+        """(pp, lt, g, span): the launch form a call takes (`viai_wav_resample_form`, host arithmetic).  A tile is lt * g * pp consecutive
+        outputs and stages span words of LDS.  pp = 4: the period form (lt = L, four outputs per work item, g periods per pass); pp = 1: the
+        consecutive form (one output per item, lt of 1024 .. 64); pp = 0: no tile fits 64 KiB of LDS and a call is refused."""
+        v = [C.c_int() for _ in range(4)]
+        _lib.check(_lib.load().viai_wav_resample_form(self.L, self.M, self.H, *[C.byref(x) for x in v]), "viai_wav_resample_form")
+        return tuple(x.value for x in v)
+
     def __call__(self, wav, lengths=None, out=None, window=None, out_len=None):
         """wav (B, n) floats on the GPU -> (B, m), m = ceil(n L / M), or (B, out_len).
 
