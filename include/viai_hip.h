@@ -651,6 +651,54 @@ int viai_janssen_fill_host(const float* wav, const int* lengths, long stride, in
 int viai_janssen_plan_host(const int* lengths, int B, long n, const int* count, const int* start, const int* length, int K, int order,
                            int context, int max_len, int* leader, int* win_lo, int* win_hi, int* unknowns);
 
+/* ---- declipping: bound-constrained Janssen AR restoration (csrc/declip.hip, csrc/viai_declip_rule.h on csrc/viai_janssen_rule.h and
+ * csrc/viai_ar_rule.h; additive to ABI v20) ----
+ * A clipped sample carries two facts a dropout does not: its sign, and a lower bound on its magnitude.  viai_janssen_fill uses neither, and
+ * clipped voiced sound (a run at every peak) makes its clusters close on capacity, each a wall for the next.  Here the same joint solve runs
+ * under the bounds, on windows that are NOT cut at neighbouring entries, and several launches (SWEEPS) hand the estimates of one cluster to the
+ * windows of the others.  fp64 arithmetic of + - * / and comparisons only, each operation rounded once, every sum one of viai_janssen_fill's:
+ * the kernel and the host mirror call the same functions of csrc/viai_declip_rule.h and give the same bits.
+ * Three buffers: ref (B, stride) is the clip as recorded and gives the bounds; src (B, stride) holds the current estimates and is read
+ * everywhere (the first sweep passes src = ref); out (B, out_stride) is written at the unknowns only and must not overlap src or ref.  Rows,
+ * len, listed, entries and front_k as for viai_janssen_fill.
+ *   USABLE, CLUSTERS  exactly those of viai_janssen_fill, limits and capacity tests included.
+ *   WINDOW    [max(s_first - context, 0), min(e_last + context, len)); W <= 4096 by the cluster rule.  It is NOT cut at neighbouring entries:
+ *             samples of other clusters' entries (and of skipped entries) inside it are knowns, read from src -- the recorded values in the
+ *             first sweep, the previous sweep's estimates later.  That is why out may not be src.  A non-finite known reads as 0.0.
+ *   BOUND     for unknown i at window position t_i, c_i = ref[t_i] in fp64, a non-finite one read as 0.0.  c_i > 0: x_i >= c_i; c_i < 0:
+ *             x_i <= c_i; c_i == 0 (a dropout, a non-finite sample): free.  x VIOLATES when the comparison is not true (so a NaN violates).
+ *   START     the estimates start at src[t_i] (fp64, non-finite as 0.0), not at 0.0.  p = min(order, W / 2); p < 1: the start values are
+ *             written, filled = 4.
+ *   ITERATE   iters times:
+ *             fit     a[0 .. p] = Burg's fit of viai_ar_fill on the window with the current estimates; b_l as viai_janssen_fill.  All pins
+ *                     are cleared.
+ *             solve   viai_janssen_fill's solve for all M unknowns (G, r, L D L^T, unchanged; x0 holds 0.0 at the unknowns).
+ *             pin     up to `rounds` times: every unknown that is not pinned and violates becomes PINNED: x_i = c_i, and x0[t_i] = c_i.  If
+ *                     none was pinned in this round, or no unknown is left free, the rounds end.  Otherwise the free unknowns, compacted in
+ *                     position order f(0) < f(1) < ... < f(M' - 1), are solved again with the same a: G'_qr = b_{|t_f(q) - t_f(r)|} inside p,
+ *                     r'_q = 0.0 - sum_l b_{|l|} x0[t_f(q) + l] (the pinned ones are knowns of value c), the same banded L D L^T over M'.
+ *             clamp   if rounds >= 1: every unknown that still violates is set to c_i.  Then the estimates <- x, and x0 is 0.0 at every
+ *                     unknown again.  With rounds = 0 nothing is pinned and nothing is clamped: the unconstrained wide-window solve.
+ *             A pivot that is not > 0.0 or not finite, in ANY solve, stops the cluster: the estimates of the last completed iteration stay
+ *             (the start values when none completed), filled = 5.
+ *   SUMS      those of viai_janssen_fill.  The compaction is an exclusive count in position order: integers only.
+ *   WRITE     out[t_i] = (float)x_i, one rounding, at the unknowns only.  Rounding is monotone and c_i is an fp32 value, so with rounds >= 1
+ *             every sample written with filled = 1 satisfies its bound in fp32.
+ *   filled    as viai_janssen_fill: 1, 4, 5, and 0 for skipped or not listed.
+ * This is an active-set HEURISTIC WITHOUT RELEASE, not an exact quadratic program: a pinned unknown stays pinned until the next fit even when
+ * the re-solve would let it go, and the clamp is a projection.
+ * ONE launch per call (a sweep), one block of 256 threads per (row, entry index) as viai_janssen_fill; no atomics (the pin bitmap is a word per
+ * wave, the compaction ballots and a four-wave exclusive sum), no workspace, nothing synced; dynamic LDS 143 696 bytes per block.
+ * Refuses with hipErrorInvalidValue before any launch: what viai_janssen_fill refuses (for ref, src and out alike), rounds outside 0 .. 8,
+ * and out overlapping src or ref ([p, p + 4 ((B - 1) stride + n)) as byte ranges).                                                              */
+int viai_declip(const float* ref, const float* src, const int* lengths, long stride, int B, long n, const int* count, const int* start,
+                const int* length, int K, int order, int context, int max_len, int iters, int rounds, float* out, long out_stride, int* filled,
+                void* stream);
+/* the same rule with plain loops from the same header, every pointer in HOST memory.  Same refusals (the alignment rule apart).                */
+int viai_declip_host(const float* ref, const float* src, const int* lengths, long stride, int B, long n, const int* count, const int* start,
+                     const int* length, int K, int order, int context, int max_len, int iters, int rounds, float* out, long out_stride,
+                     int* filled);
+
 /* ---- clicks: impulsive damage found in a prediction residual (csrc/click_detect.hip, csrc/viai_click_rule.h; additive to ABI v20) ----
  * A click is neither silent nor clipped nor non-finite, so viai_gap_detect cannot see it.  Here an all-pole model is fitted to a stretch of the
  * signal, the signal is run through the inverse (prediction-error) filter, and a click is where the squared residual stands far above its own

@@ -18,6 +18,7 @@ name; the top-level `viai_amd/` shim maps the import name onto it).
                 janssen_plan_host
   click_detect  where a clip holds clicks: find_clicks (outliers of an AR prediction residual; HIP), find_clicks_host, declick, declick_host,
                 declick_file
+  declip        clipped peaks restored under their bounds: declip_fill (bound-constrained Janssen; HIP), declip_fill_host, declip, declip_file
   video     raw frames and flow maps -> the visual branch's blocks: motion_box, resize_u8, prepare, VideoFrontEnd (HIP), motion_box_host
   optical_flow  raw frames -> TV-L1 flow -> the 8-bit flow maps `video` takes: tvl1, encode_u8, flow_u8 (HIP), tvl1_host, encode_u8_host
   wav_io    WAV in, WAV out: parse_wav, decode_pcm / encode_pcm / patch_pcm (HIP) and their _host mirrors, read_wav, write_wav, save_wav, repair_file
@@ -49,4 +50,8 @@ def __getattr__(name):
     if name in ("find_clicks", "find_clicks_host", "declick", "declick_host", "declick_file"):
         from . import click_detect
         return getattr(click_detect, name)
+    if name in ("declip_fill", "declip_fill_host", "declip", "declip_file"):
+        import importlib
+        mod = importlib.import_module(".declip", __name__)                  # the module is callable: viai_amd.declip(wav, clip) is its declip()
+        return mod if name == "declip" else getattr(mod, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -182,6 +182,8 @@ SIGNATURES = {
     "viai_janssen_fill": (_I, [_P, _P, _L, _I, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
     "viai_janssen_fill_host": (_I, [_P, _P, _L, _I, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P]),
     "viai_janssen_plan_host": (_I, [_P, _I, _L, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "viai_declip": (_I, [_P, _P, _P, _L, _I, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
+    "viai_declip_host": (_I, [_P, _P, _P, _L, _I, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
     "viai_click_detect_ws_bytes": (_L, [_I, _L, _I]),
     "viai_click_detect": (_I, [_P, _P, _L, _I, _L, _I, _F, _I, _I, _F, _I, _I, _I, _P, _P, _P, _P, _P]),
     "viai_click_detect_host": (_I, [_P, _P, _L, _I, _L, _I, _F, _I, _I, _F, _I, _I, _I, _P, _P, _P]),
