@@ -254,6 +254,28 @@ def case_by_name(name):
     return next(c for c in all_cases() if c["name"] == name)
 
 
+# ------------------------------------------------------------------------------------------------------------------------------ a long row
+# 257 tiles: each thread of the shared gd_rows_kernel owns two, so E = 2 TILE is a thread edge (tests/gap_detect_common.py pins that launch to
+# numpy at this length).  Not part of `all_cases()`: its base signal is a Python loop over a million samples.
+LONG_N = 256 * TILE + 1
+LONG_LENGTHS = (LONG_N, 255 * TILE + 9)
+_LONG = []
+
+
+def long_clicks():
+    """clicks `guard` samples either side of two thread edges (the dilation crosses them), in the last full tile, on the last sample of the
+    shorter row and on the last sample"""
+    E, g = 2 * TILE, DEFAULTS["guard"]
+    return [E - g, E + g, 64 * E - g, 64 * E + g, 255 * TILE + 8, 255 * TILE + 100, 255 * TILE + 2000, LONG_N - 1]
+
+
+def long_case():
+    if not _LONG:
+        rows = np.stack([clicked(seed, n=LONG_N, at=long_clicks())[1] for seed in (11, 12)])
+        _LONG.append(case("long 256 T + 1", rows, lengths=LONG_LENGTHS))
+    return _LONG[0]
+
+
 def measured_margin():
     """4 x the largest relative difference of q / threshold between the two restatements over the judged samples of the table, and the number
     of judged samples compared"""

@@ -296,6 +296,33 @@ def case_by_name(name):
     return next(c for c in all_cases() if c["name"] == name)
 
 
+# ------------------------------------------------------------------------------------------------------------------------------ a long row
+# 257 tiles of `find_gaps` (T = 4096), two per thread of its row launch: the speech-like signal repeated at a quarter of its level, so under
+# the clip level, except in two stretches where it is at full level and clipped: one over the thread edge 2 T, one that ends with the row,
+# in whose one-sample last tile the signal's largest peak lies.
+LONG_T = 4096
+LONG_N = 256 * LONG_T + 1
+LONG_MAX_GAPS = 256
+LONG_STRETCHES = ((2 * LONG_T - 300, 2 * LONG_T + 300), (LONG_N - 400, LONG_N))
+_LONG = []
+
+
+def long_row():
+    """(1, LONG_N) float32"""
+    if not _LONG:
+        clean = speechlike(7)[0]
+        top = int(np.argmax(np.abs(clean)))
+        assert top >= 400 and abs(float(clean[top])) == 1.0
+        wav = (np.tile(clean, -(-LONG_N // clean.size))[:LONG_N] * np.float32(0.25)).astype(np.float32)
+        (s0, e0), (s1, e1) = LONG_STRETCHES
+        wav[s0:e0] = np.clip(clean[600:600 + e0 - s0], np.float32(-CLIP), np.float32(CLIP))
+        wav[s1:e1] = np.clip(clean[top + 1 - (e1 - s1):top + 1], np.float32(-CLIP), np.float32(CLIP))
+        wav = wav[None, :].copy()
+        wav.setflags(write=False)
+        _LONG.append(wav)
+    return _LONG[0]
+
+
 _HOST = {}
 
 

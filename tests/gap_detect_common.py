@@ -46,15 +46,29 @@ def merged_runs(runs, min_len, merge_within):
     return out
 
 
-def rule(wav, n, lengths=None, threshold=0.0, clip=0.0, min_len=64, merge_within=0, max_gaps=16):
-    """-> (count (B,), start (B, K), length (B, K)) int32"""
+def raw_runs_fast(row, length, threshold, clip):
+    """step 1 on whole arrays, for rows of millions of samples: the damage mask with the same fp32 comparisons, run edges from the differences
+    of the zero-padded mask.  tests/test_gap_detect_cpu.py holds it equal to `raw_runs` on every row of `all_cases()`."""
+    threshold, clip = np.float32(threshold), np.float32(clip)
+    x = np.asarray(row[:length], dtype=np.float32)
+    with np.errstate(invalid="ignore"):
+        a = np.abs(x)
+        bad = ~np.isfinite(x) | (a <= threshold)
+        if clip > 0:
+            bad |= a >= clip
+    edge = np.diff(np.concatenate(([0], bad.astype(np.int8), [0])))
+    return list(zip(np.flatnonzero(edge == 1).tolist(), np.flatnonzero(edge == -1).tolist()))
+
+
+def rule(wav, n, lengths=None, threshold=0.0, clip=0.0, min_len=64, merge_within=0, max_gaps=16, raw=raw_runs):
+    """-> (count (B,), start (B, K), length (B, K)) int32; raw: `raw_runs` or `raw_runs_fast`"""
     B, K = wav.shape[0], max_gaps
     count = np.zeros(B, dtype=np.int32)
     start = np.zeros((B, K), dtype=np.int32)
     length = np.zeros((B, K), dtype=np.int32)
     for b in range(B):
         ln = n if lengths is None else min(max(int(lengths[b]), 0), n)
-        runs = merged_runs(raw_runs(wav[b], ln, threshold, clip), min_len, merge_within)
+        runs = merged_runs(raw(wav[b], ln, threshold, clip), min_len, merge_within)
         count[b] = len(runs)
         for k, (s, e) in enumerate(runs[:K]):
             start[b, k], length[b, k] = s, e - s
@@ -66,7 +80,7 @@ _EXPECTED = {}
 
 def expected(case):
     if case["name"] not in _EXPECTED:
-        got = rule(case["wav"], case["n"], case["lengths"], **case["kw"])
+        got = rule(case["wav"], case["n"], case["lengths"], raw=raw_runs_fast if case.get("fast") else raw_runs, **case["kw"])
         for a in got:
             a.setflags(write=False)
         _EXPECTED[case["name"]] = got
@@ -226,6 +240,84 @@ def case_names():
 
 def case_by_name(name):
     return next(c for c in all_cases() if c["name"] == name)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ long rows
+# gd_rows_kernel gives thread k of its 256 the tiles [k per, (k + 1) per), per = ceil(tiles / 256): above 256 T samples a thread walks more than
+# one tile.  Two lengths: 257 tiles (per 2: thread 128 owns one tile of one sample, threads 129 .. 255 none) and 601 tiles (per 3: thread 200
+# owns one tile of 5 samples).  Both are odd, so every row behind the first takes the 4-byte loads.  E = per T is a "thread edge".
+# The rule is `raw_runs_fast`; a group's rows are built when one of its cases is asked for, and only the last group is kept (60 MB at the most).
+ROWS_THREADS = 256                                                        # GD_THREADS
+LONG_N = {2: 256 * T + 1, 3: 600 * T + 5}
+LONG_RANDOM_P = (0.02, 0.5)
+
+
+def long_rows(group):
+    kind, per = group[0], group[1]
+    n, E = LONG_N[per], per * T
+    L = (n - 1) // T * T                                                  # where the last tile starts
+    if kind == "geometry":
+        return rows_with(n, [[(E + T - 3, E + T + 3)],                    # across a tile edge inside thread 1's range
+                             [(E - 3, E + 3)],                            # across a thread edge
+                             [(E + T - 5, 5 * E + T + 7)],                # over several threads' whole ranges (3 T - 5 .. 11 T + 7 at per 2)
+                             [(0, n)],                                    # the whole row
+                             [(100 * T + 9, n)],                          # from the middle to the end: no good sample behind, the run ends at len
+                             [(n - 1, n)]])                               # the lone last sample (kept with min_len 1 only)
+    if kind == "merging":
+        return rows_with(n, [[(E - 13, E - 3), (E + 3, E + 13)],          # two kept runs 6 apart facing each other across a thread edge
+                             [(2 * E - 16, 2 * E - 4), (2 * E - 2, 2 * E + 1), (2 * E + 2, 2 * E + 12)],     # kept, dropped (on the edge), kept: 6
+                             [(E + T - 13, E + T - 3), (E + T + 3, E + T + 13)]])      # the pair across a tile edge inside thread 1's range
+    if kind == "overflow":
+        far = (n // T) // 10 * T                                          # ten runs 25 tiles apart (60 at per 3): later tiles have off > K
+        return rows_with(n, [[(k * far + 17 * k + 100, k * far + 17 * k + 110) for k in range(10)],
+                             [(j * E - 5, j * E + 5) for j in range(3, 3 + 10 * 12, 12)]])       # ten runs on thread edges
+    if kind == "ragged":
+        runs = [(E - 6, E + 6), (5 * E, 5 * E + 9), (L - 4, n)]           # on a thread edge, from one, into the last tile
+        return rows_with(n, [runs] * 5)
+    assert kind == "random"
+    g = np.random.default_rng(1000 * per + int(100 * group[2]))
+    wav = g.uniform(0.1, 0.9, size=(2, n)).astype(np.float32)
+    wav[g.random((2, n)) < group[2]] = 0.0
+    return wav
+
+
+def _long_table():
+    out = []
+    for per, n in sorted(LONG_N.items()):
+        E, L, tag = per * T, (n - 1) // T * T, "long per=%d " % per
+        out.append((tag + "geometry min_len=4", ("geometry", per), None, {}))
+        out.append((tag + "geometry min_len=1", ("geometry", per), None, dict(min_len=1)))
+        out.append((tag + "merging within 6", ("merging", per), None, dict(merge_within=6)))
+        out.append((tag + "merging within 5", ("merging", per), None, dict(merge_within=5)))
+        out.append((tag + "overflow K=3", ("overflow", per), None, dict(max_gaps=3)))
+        out.append((tag + "K=1 merging all", ("overflow", per), None, dict(max_gaps=1, merge_within=n)))
+        out.append((tag + "ragged", ("ragged", per), np.array([0, E, L + 1, n + 50, -3], dtype=np.int32), {}))
+        for p in LONG_RANDOM_P:
+            for min_len, merge_within in RANDOM_RULES:
+                out.append((tag + "random p=%g min_len=%d merge=%d" % (p, min_len, merge_within), ("random", per, p), None,
+                            dict(min_len=min_len, merge_within=merge_within, max_gaps=64)))
+    assert len({r[0] for r in out}) == len(out)
+    return out
+
+
+_LONG_TABLE = _long_table()
+_LONG_ROWS = {}
+
+
+def long_case_names():
+    return [r[0] for r in _LONG_TABLE]
+
+
+def long_case_by_name(name):
+    """the case, its rule the vectorised one; the rows of its group are shared with the group's other cases and must not be written"""
+    _, group, lengths, kw = next(r for r in _LONG_TABLE if r[0] == name)
+    if group not in _LONG_ROWS:
+        _LONG_ROWS.clear()
+        _LONG_ROWS[group] = long_rows(group)
+    c = case(name, _LONG_ROWS[group], lengths=lengths, **kw)
+    assert c["wav"].shape[0] <= 8
+    c["fast"] = True
+    return c
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ repair()

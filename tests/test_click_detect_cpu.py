@@ -45,6 +45,24 @@ def test_host_mirror_equals_the_restatement_exactly(name):
     assert np.array_equal(got.start, want.start) and np.array_equal(got.length, want.length)
 
 
+def test_host_mirror_equals_the_restatement_on_a_long_row():
+    """257 tiles (click_detect_common.long_case): the runs that the GPU test compares the device with are the restatement's, and they are where
+    the clicks were planted -- across both thread edges, in the last full tile, nothing in row 0's one-sample last tile"""
+    c = K.long_case()
+    got, want = host(c), K.rule_exact(c)
+    assert np.array_equal(got.count, want.count) and np.array_equal(got.start, want.start) and np.array_equal(got.length, want.length)
+    E, g = 2 * K.TILE, K.DEFAULTS["guard"]
+    assert 0 < int(got.count.max()) <= K.DEFAULTS["max_gaps"]
+    for b, ln in enumerate(K.LONG_LENGTHS):
+        rs = runs(got, b)
+        for edge in (E, 64 * E):
+            assert any(st <= edge - 2 * g and edge + 2 * g < st + n for st, n in rs), (b, edge)        # one run over the edge, guards included
+        assert all(st + n <= ln for st, n in rs)
+    covers = lambda rs, at: any(st <= at < st + n for st, n in rs)
+    assert covers(runs(got, 0), 255 * K.TILE + 100) and covers(runs(got, 0), 255 * K.TILE + 2000) and not covers(runs(got, 0), K.LONG_N - 1)
+    assert not covers(runs(got, 1), 255 * K.TILE + 100)                    # behind row 1's length
+
+
 def test_the_table_finds_something():
     """the comparison above is not one of empty lists"""
     assert runs(host(K.case_by_name("base"))) and int(host(K.case_by_name("overflow")).count[0]) == 12

@@ -2,7 +2,9 @@
 tests/click_detect_common.py (n = 1, 63, 4096, 4097 and 2 * 4096 + 777, ragged lengths, rows that are 4-byte but not 16-byte aligned, order 1
 and 128, guard 0 and 64, clicks on both sides of a tile boundary, B = 1 and 5); it repeats, and a row alone is the row in a batch; `declick`
 equals `find_clicks_host` + `ar_fill_host` bit for bit and reads the lists where they lie; `declick_file` changes only the bytes of the listed
-runs.  The largest clip is 8969 samples."""
+runs.  The largest clip of the table is 8969 samples; test_device_equals_the_host_mirror_on_a_long_row and
+test_declick_of_a_long_row_equals_the_host_mirrors_bit_for_bit run 2 rows of 256 * 4096 + 1 samples (257 tiles: gd_rows_kernel with two tiles per
+thread, cd_dilate_kernel and gd_emit_kernel at tile indices far into a row)."""
 import numpy as np
 import pytest
 import torch
@@ -49,6 +51,27 @@ def test_device_equals_the_host_mirror_exactly(name):
     assert torch.equal(bits(wav), bits(kept))                             # the input is not written
     again = find_clicks(wav, **K.call_kwargs(c))
     assert all(torch.equal(a, b) for a, b in zip(again, got))
+
+
+def test_device_equals_the_host_mirror_on_a_long_row():
+    """257 tiles, so each thread of gd_rows_kernel owns two and cd_dilate_kernel / gd_emit_kernel index tiles far into the row: clicks whose
+    dilation crosses a thread edge, clicks in the last full tile and on the last sample, lengths [n, 255 T + 9]"""
+    from viai_amd.click_detect import find_clicks
+    c = K.long_case()
+    got = find_clicks(on_device(c), **K.call_kwargs(c))
+    same(got, host(c))
+    assert int(got.count[0]) >= 5 and int(got.count[1]) >= 2              # two thread edges, and in row 0 three clicks in the last full tile
+
+
+def test_declick_of_a_long_row_equals_the_host_mirrors_bit_for_bit():
+    from viai_amd.click_detect import declick, declick_host
+    c = K.long_case()
+    out, gaps, filled = declick(on_device(c), lengths=c["lengths"])
+    want, want_gaps, want_filled = declick_host(K.clip(c), lengths=c["lengths"])
+    same(gaps, want_gaps)
+    assert np.array_equal(filled.cpu().numpy(), want_filled) and int((filled > 0).sum()) >= 8
+    assert np.array_equal(bits(out).cpu().numpy(), np.ascontiguousarray(want).view(np.int32))
+    assert not np.array_equal(want.view(np.int32), K.clip(c).view(np.int32))
 
 
 def test_a_row_view_that_is_not_16_byte_aligned():

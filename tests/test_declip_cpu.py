@@ -92,6 +92,27 @@ def test_every_solved_sample_satisfies_its_bound_and_nothing_else_changes(lib, s
     assert inside >= 1
 
 
+def test_a_long_row_lists_its_two_stretches_and_is_restored_under_its_bounds(lib):
+    """declip_common.long_row, 257 tiles of `find_gaps`: what tests/test_declip_gpu.py compares the device with.  The lists fit, their runs lie
+    in the two stretches (over a thread edge of the row launch; up to the last sample, alone in its tile), every run is solved, inside its bound"""
+    from viai_amd.declip import declip_fill_host
+    from viai_amd.gap_detect import find_gaps_host
+    wav = D.long_row()
+    gaps = find_gaps_host(wav, clip=D.CLIP, min_len=1, max_gaps=D.LONG_MAX_GAPS)
+    count = int(gaps.count[0])
+    assert 8 <= count <= D.LONG_MAX_GAPS
+    start, end = gaps.start[0, :count], gaps.start[0, :count] + gaps.length[0, :count]
+    (s0, e0), (s1, e1) = D.LONG_STRETCHES
+    first = (start >= s0) & (end <= e0)
+    assert np.all(first | ((start >= s1) & (end <= e1))) and 4 <= first.sum() <= count - 4
+    assert start[first].min() < 2 * D.LONG_T <= end[first].max() and end.max() == D.LONG_N          # both sides of the edge; the last sample
+    out, filled = declip_fill_host(wav, gaps)
+    assert (filled[0, :count] == 1).all() and (filled[0, count:] == 0).all()
+    solved = D.listed_mask(gaps, wav.shape, filled, 1)
+    assert solved.sum() >= count and D.violations(wav, out, solved) == 0
+    assert np.array_equal(bits(out)[~solved], bits(wav)[~solved])
+
+
 # ----------------------------------------------------------------------------- 3. quality against the project's own baseline
 @pytest.mark.parametrize("seed", D.SEEDS)
 def test_declipping_beats_janssen_fill_by_3_db_on_clipped_voiced_sound(lib, seed):

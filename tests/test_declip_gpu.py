@@ -1,7 +1,8 @@
 """GPU: `declip_fill` (csrc/declip.hip) against its host mirror BIT FOR BIT, on `out` and on `filled`: the case table of tests/declip_common.py
 (M = 1; every sample pinned, so no second solve; 300 unknowns compacted across all four waves; order 80; windows cut by both row ends; K
 larger than count; an all-zero window; no model; a long noiseless run; a mixed list), the 3-cluster speech-like rows at 1, 2 and 3 sweeps, a
-row alone against the same row inside a batch of 8; then `declip` against `find_gaps` + `declip_fill`, and `declip_file` on a 16-bit file.
+row alone against the same row inside a batch of 8; then `declip` against `find_gaps` + `declip_fill`, `declip` on a row of 256 * 4096 + 1
+samples against the host mirrors (test_declip_of_a_long_row_equals_the_host_mirrors: 257 tiles of `find_gaps`), and `declip_file` on a 16-bit file.
 The mirror itself is pinned to the numpy restatement by tests/test_declip_cpu.py."""
 import numpy as np
 import pytest
@@ -90,6 +91,21 @@ def test_declip_is_find_gaps_then_declip_fill_with_the_lists_on_the_device():
     import viai_amd
     out2, _, _ = viai_amd.declip(wav, D.CLIP, max_gaps=256, sweeps=2)                           # the package attribute is the same call
     assert torch.equal(out2.view(torch.int32), out.view(torch.int32))
+
+
+def test_declip_of_a_long_row_equals_the_host_mirrors():
+    """257 tiles of `find_gaps`, two per thread of its row launch (declip_common.long_row): clipped runs over a thread edge and up to the last
+    sample, which is alone in its tile.  The lists are the host's as integers, `out` and `filled` the host's bit for bit."""
+    from viai_amd.declip import declip, declip_fill_host
+    from viai_amd.gap_detect import find_gaps_host
+    wav = D.long_row()
+    out, gaps, filled = declip(torch.from_numpy(wav.copy()).cuda(), D.CLIP, max_gaps=D.LONG_MAX_GAPS)
+    want_gaps = find_gaps_host(wav, clip=D.CLIP, min_len=1, max_gaps=D.LONG_MAX_GAPS)
+    assert 0 < int(gaps.count[0]) <= D.LONG_MAX_GAPS                                            # the lists hold every run
+    assert all(g.dtype == torch.int32 and np.array_equal(g.cpu().numpy(), w) for g, w in zip(gaps, want_gaps))
+    want, want_filled = declip_fill_host(wav, want_gaps)
+    assert np.array_equal(filled.cpu().numpy(), want_filled) and int((want_filled == 1).sum()) == int(want_gaps.count[0])
+    assert np.array_equal(bits(out.cpu().numpy()), bits(want)) and not np.array_equal(bits(want), bits(wav))
 
 
 @pytest.mark.parametrize("clip", [9830.0 / 32768.0, None])

@@ -1,6 +1,8 @@
 """CPU: the gap-detection rule (include/viai_hip.h) without a device.  The numpy statement of the rule gives lists written out by
 hand; `find_gaps_host` (plain C++, sample by sample) equals it exactly on every case the GPU test runs; the workspace size is host arithmetic; and
-`viai_gap_detect` refuses bad arguments before any launch, so also here."""
+`viai_gap_detect` refuses bad arguments before any launch, so also here.  The vectorised statement `raw_runs_fast` equals the sample loop on
+every row of the table, and with it `find_gaps_host` equals the rule on the long rows of the GPU test (256 T + 1 and 600 T + 5 samples:
+test_find_gaps_host_equals_the_numpy_rule_on_long_rows)."""
 import ctypes as C
 import os
 import re
@@ -106,6 +108,60 @@ def test_find_gaps_host_equals_the_numpy_rule(name):
     got = find_gaps_host(c["wav"][:, :c["n"]], lengths=c["lengths"], **c["kw"])
     want = G.expected(c)
     for g, w, what in zip(got, want, ("count", "start", "length")):
+        assert g.dtype == np.int32 and g.shape == w.shape and np.array_equal(g, w), what
+
+
+# ----------------------------------------------------------------------------- 2b. rows of millions of samples (gap_detect_common.long_rows)
+def test_the_vectorised_rule_is_the_sample_loop_on_every_row_of_the_table():
+    rows = 0
+    for c in G.all_cases():
+        kw = dict(threshold=0.0, clip=0.0)
+        kw.update(c["kw"])
+        for b in range(c["wav"].shape[0]):
+            ln = c["n"] if c["lengths"] is None else min(max(int(c["lengths"][b]), 0), c["n"])
+            assert G.raw_runs_fast(c["wav"][b], ln, kw["threshold"], kw["clip"]) == G.raw_runs(c["wav"][b], ln, kw["threshold"], kw["clip"]), (c["name"], b)
+            rows += 1
+    assert rows == 311 and len(G.all_cases()) == 56
+
+
+def test_the_long_cases_say_what_their_names_say():
+    """the lengths put more than one tile on a thread of gd_rows_kernel, and the runs lie on the edges the builders name"""
+    T = G.T
+    for per, n in G.LONG_N.items():
+        ntiles = -(-n // T)
+        assert -(-ntiles // G.ROWS_THREADS) == per and n % 2 == 1 and n > G.ROWS_THREADS * T
+        last_owner, left = (ntiles - 1) // per, ntiles - (ntiles - 1) // per * per
+        assert (per, ntiles, last_owner, left, n - (ntiles - 1) * T) in ((2, 257, 128, 1, 1), (3, 601, 200, 1, 5))
+        E, tag = per * T, "long per=%d " % per
+        count, start, length = G.expected(G.long_case_by_name(tag + "geometry min_len=4"))
+        assert list(count) == [1, 1, 1, 1, 1, 0] and list(start[:5, 0]) == [E + T - 3, E - 3, E + T - 5, 0, 100 * T + 9]
+        assert list(length[:5, 0]) == [6, 6, 4 * E + 12, n, n - 100 * T - 9]
+        count, start, length = G.expected(G.long_case_by_name(tag + "geometry min_len=1"))
+        assert (count[5], start[5, 0], length[5, 0]) == (1, n - 1, 1)
+        joined, apart = G.expected(G.long_case_by_name(tag + "merging within 6")), G.expected(G.long_case_by_name(tag + "merging within 5"))
+        assert list(joined[0]) == [1, 1, 1] and list(apart[0]) == [2, 2, 2]
+        assert list(joined[1][:, 0]) == [E - 13, 2 * E - 16, E + T - 13] and list(joined[2][:, 0]) == [26, 28, 26]
+        assert list(apart[1][1, :2]) == [2 * E - 16, 2 * E + 2]                      # the dropped run on the edge is not listed
+        count, start, length = G.expected(G.long_case_by_name(tag + "overflow K=3"))
+        assert list(count) == [10, 10] and start[0, 2] > 2 * 25 * T and list(start[1]) == [3 * E - 5, 15 * E - 5, 27 * E - 5]
+        count, start, length = G.expected(G.long_case_by_name(tag + "K=1 merging all"))
+        assert list(count) == [1, 1] and list(start[:, 0]) == [100, 3 * E - 5] and list(length[1]) == [108 * E + 10]
+        c = G.long_case_by_name(tag + "ragged")
+        count, start, length = G.expected(c)
+        L = (ntiles - 1) * T
+        assert list(c["lengths"]) == [0, E, L + 1, n + 50, -3] and list(count) == [0, 1, 3, 3, 0]
+        assert (start[1, 0], length[1, 0]) == (E - 6, 6) and (start[2, 2], length[2, 2]) == (L - 4, 5) and length[3, 2] == n - L + 4
+        for p in G.LONG_RANDOM_P:
+            count, _, _ = G.expected(G.long_case_by_name(tag + "random p=%g min_len=1 merge=0" % p))
+            assert count.min() > 64 * 100                                 # runs in every tile: every thread's loops carry
+
+
+@pytest.mark.parametrize("name", G.long_case_names())
+def test_find_gaps_host_equals_the_numpy_rule_on_long_rows(name):
+    from viai_amd.gap_detect import find_gaps_host
+    c = G.long_case_by_name(name)
+    got = find_gaps_host(c["wav"], lengths=c["lengths"], **c["kw"])
+    for g, w, what in zip(got, G.expected(c), ("count", "start", "length")):
         assert g.dtype == np.int32 and g.shape == w.shape and np.array_equal(g, w), what
 
 

@@ -3,8 +3,18 @@ integers -- on every case of tests/gap_detect_common.py (T = VIAI_GAP_DETECT_TIL
 whole tiles; the predicate's edge values; ragged rows; merging; overflow; random damage at three densities), and `repair` is the hand-written
 sequence of `AudioInpainter` calls.
 
-Sizes: the largest clip is 8 T + 5 = 32 773 samples; rows that are 16-byte aligned take the kernel's float4 loads, the others (odd n, odd
-strides) its 4-byte loads."""
+Sizes: the largest clip of the shared table is 8 T + 5 = 32 773 samples; rows that are 16-byte aligned take the kernel's float4 loads, the others
+(odd n, odd strides) its 4-byte loads.
+
+Long rows (`gap_detect_common.long_rows`; the rule is the vectorised `raw_runs_fast`).  Above 256 T = 1 048 576 samples a thread of
+gd_rows_kernel owns per = ceil(tiles / 256) > 1 tiles, and its four tile loops, the block scans fed by them, and gd_emit_kernel's tile
+indices and `off > K` return far into a row run for the first time:
+    test_find_gaps_equals_the_numpy_rule_on_long_rows               n = 256 T + 1 (257 tiles, per 2) and 600 T + 5 (601 tiles, per 3): runs over
+                                                                    tile edges inside a thread's range and over thread edges, over several
+                                                                    threads' ranges, to the end of the row, the lone last sample, merging
+                                                                    across an edge, overflow, ragged lengths, random damage
+    test_entries_behind_the_runs_are_written_as_zero_on_long_rows   the two overflow cases on sentinel-filled outputs
+    test_a_long_row_alone_is_its_row_in_the_batch                   the ragged case"""
 import gc
 
 import numpy as np
@@ -55,9 +65,13 @@ def test_lengths_may_live_on_the_device():
 @pytest.mark.parametrize("name", ["overflow K=3", "overflow K=1", "overflow K=1 merging", "geometry n=1 min_len=1", "merging within 10"])
 def test_entries_behind_the_runs_are_written_as_zero(name):
     """the C call on outputs filled with a sentinel: count is the true number, the first K runs are there, everything behind them is 0"""
+    check_sentinel_filled_outputs(G.case_by_name(name), name.startswith("overflow"))
+
+
+def check_sentinel_filled_outputs(c, overflows):
     from viai_amd import _lib
     from viai_amd.ops import _stream
-    c = G.case_by_name(name)
+    name = c["name"]
     wav = on_device(c).contiguous()
     B, n = wav.shape
     kw = dict(threshold=0.0, clip=0.0, merge_within=0)
@@ -77,8 +91,36 @@ def test_entries_behind_the_runs_are_written_as_zero(name):
         k = min(int(cnt[b]), K)
         assert int(start[b, k:].abs().sum()) == 0 and int(length[b, k:].abs().sum()) == 0
         assert int((length[b, :k] > 0).sum()) == k
-    if name.startswith("overflow"):
+    if overflows:
         assert int(cnt.max()) > K                                         # the case overflows, as its name says
+
+
+# ----------------------------------------------------------------------------- 2b. rows of more than 256 tiles: a thread of launch 2 walks 2 or 3
+@pytest.mark.parametrize("name", G.long_case_names())
+def test_find_gaps_equals_the_numpy_rule_on_long_rows(name):
+    from viai_amd.gap_detect import find_gaps
+    c = G.long_case_by_name(name)
+    assert_gaps(find_gaps(on_device(c), lengths=c["lengths"], **c["kw"]), G.expected(c), name)
+
+
+@pytest.mark.parametrize("per", sorted(G.LONG_N))
+def test_entries_behind_the_runs_are_written_as_zero_on_long_rows(per):
+    """tiles far behind the K-th run return from launch 3 at once (off > K); with everything merged launch 2 writes the one length"""
+    check_sentinel_filled_outputs(G.long_case_by_name("long per=%d overflow K=3" % per), True)
+    check_sentinel_filled_outputs(G.long_case_by_name("long per=%d K=1 merging all" % per), False)
+
+
+@pytest.mark.parametrize("per", sorted(G.LONG_N))
+def test_a_long_row_alone_is_its_row_in_the_batch(per):
+    from viai_amd.gap_detect import find_gaps
+    c = G.long_case_by_name("long per=%d ragged" % per)
+    wav = on_device(c)
+    whole = find_gaps(wav, lengths=c["lengths"], **c["kw"])
+    assert_gaps(whole, G.expected(c))
+    for b in range(wav.size(0)):
+        alone = find_gaps(wav[b:b + 1], lengths=c["lengths"][b:b + 1], **c["kw"])      # rows 1 ..: 4-byte aligned only, alone or in the batch
+        for a, w in zip(alone, whole):
+            assert torch.equal(a[0], w[b]), b
 
 
 # ----------------------------------------------------------------------------- 3. a row alone, a row in a batch, a second call

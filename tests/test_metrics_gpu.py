@@ -1,9 +1,15 @@
 """GPU: the inpainting metrics (`viai_amd.metrics`, csrc/metrics.hip) against their fp64 numpy restatement (tests/metrics_common.py).
 
 Bounds.  The kernels sum fp64 terms made from fp32 inputs; a product or difference of two floats is exact in double, so the only error of a sum is
-its order: at most count * 2^-53 relative to the sum of the terms' magnitudes, 4.5e-12 for the longest sum here (40 001 terms).  Every sum is
+its order: at most count * 2^-53 relative to the sum of the terms' magnitudes, 2.3e-11 for the longest sum here (200 001 terms).  Every sum is
 therefore held to 1e-10 * sum |terms|, and counts are exact.  SSIM divides moments whose denominators are at least c2 = 9e-4 and shares the
-window's weights with the restatement: the per-clip mean is held to 1e-9 absolute.  Determinism is bitwise."""
+window's weights with the restatement: the per-clip mean is held to 1e-9 absolute.  Determinism is bitwise.
+
+More than 64 partials per stream (`mt_final_kernel`: lane l sums partials l, l + 64, ..., so below that every lane sums one at the most):
+    test_wave_gap_stats_past_64_chunks        gaps of 131 073 and 200 001 samples of n = 210 000: 65 and 98 chunks of 2048
+    test_mel_frame_stats_of_several_chunks    (F, T) = (5, 4101): 65 chunks of 64 frames; (80, 137): 3 chunks (`mel_frame_partial_kernel`'s
+                                              nchunk > 1, by value)
+    test_mel_ssim_past_64_tiles               (F, T) = (27, 1035) at 11 taps: 2 x 33 = 66 tiles"""
 import gc
 import math
 
@@ -47,9 +53,13 @@ WAVE_CASES = {"edges": (1000, [(0, 1), (333, 0), (1, 999)]),                 # o
               "chunks": (70001, [(12345, 40001), (70000, 1)])}               # 20 chunks from an odd start with an odd length; the clip's last sample
 
 
+# mt_final_kernel's lane l sums partials l, l + 64, ...: past 64 chunks (131 072 samples of a gap) a lane takes more than one
+WAVE_LONG = {"65 and 98 chunks": (210000, [(777, 131073), (5, 200001)])}     # lane 0 alone takes a second chunk; lanes 0 .. 33 do
+
+
 def wave_case(name):
     if ("wave", name) not in _CACHE:
-        n, gaps = WAVE_CASES[name]
+        n, gaps = WAVE_CASES[name] if name in WAVE_CASES else WAVE_LONG[name]
         B = len(gaps)
         ref, est = uniform(n, (B, n), -0.9, 0.9), uniform(n + 1, (B, n), -0.9, 0.9)
         est = (0.8 * ref + 0.2 * est).float()
@@ -60,6 +70,17 @@ def wave_case(name):
 
 @pytest.mark.parametrize("name", sorted(WAVE_CASES))
 def test_wave_gap_stats(name):
+    check_wave_gap_stats(name)
+
+
+@pytest.mark.parametrize("name", sorted(WAVE_LONG))
+def test_wave_gap_stats_past_64_chunks(name):
+    n, gaps = WAVE_LONG[name]
+    assert [-(-k // 2048) for _, k in gaps] == [65, 98] and all(s + k <= n for s, k in gaps)
+    check_wave_gap_stats(name)
+
+
+def check_wave_gap_stats(name):
     from viai_amd import metrics as M
     ref, est, gaps, want = wave_case(name)
     starts, lens = [g[0] for g in gaps], [g[1] for g in gaps]
@@ -121,6 +142,18 @@ def mel_case(F, T):
 @pytest.mark.parametrize("where", R.WHERE)
 @pytest.mark.parametrize("F,T", [(80, 37), (5, 1)])
 def test_mel_frame_stats(F, T, where):
+    check_mel_frame_stats(F, T, where)
+
+
+@pytest.mark.parametrize("where", R.WHERE)
+@pytest.mark.parametrize("F,T", [(80, 137), (5, 4101)])
+def test_mel_frame_stats_of_several_chunks(F, T, where):
+    """64 frames per block: 3 chunks, whose sum is checked for value here, and 65, where lane 0 of mt_final_kernel takes a second partial"""
+    assert -(-T // 64) in (3, 65)
+    check_mel_frame_stats(F, T, where)
+
+
+def check_mel_frame_stats(F, T, where):
     from viai_amd import metrics as M
     ref, est, mask, want = mel_case(F, T)
     got = M.mel_frame_stats(ref, est, mask, where)
@@ -192,6 +225,13 @@ def check_ssim(F, T, win, sigma):
 @pytest.mark.parametrize("F,T", SSIM_SHAPES)
 def test_mel_ssim(F, T):
     check_ssim(F, T, 11, 1.5)
+
+
+def test_mel_ssim_past_64_tiles():
+    """17 x 1025 window positions in 2 x 33 = 66 tiles of 16 x 32: lanes 0 and 1 of mt_final_kernel take a second partial"""
+    F, T, win = 27, 1035, 11
+    assert (-(-(F - win + 1) // 16), -(-(T - win + 1) // 32)) == (2, 33)
+    check_ssim(F, T, win, 1.5)
 
 
 def test_mel_ssim_with_another_window():

@@ -1,7 +1,8 @@
 """CPU: WAV in, WAV out (include/viai_hip.h) without a device.  The numpy statement of the PCM rule on values written out by hand;
 the host mirrors (plain C++ from csrc/viai_pcm_rule.h) equal it bit for bit over the table the GPU test runs; which formats round-trip and which
 one does not; the reference's save_wav bytes from tests/golden/wav_io.npz; scipy and the stdlib read what write_wav's layout holds; parse_wav;
-and every entry point refuses bad arguments before any launch, so also here.  No tolerance anywhere."""
+and every entry point refuses bad arguments before any launch, so also here.  No tolerance anywhere.  Section 2b holds the host mirrors to the
+numpy rule on the long clips of the GPU test (2 098 181 frames; a peak behind partial 255; a run of 24 653 samples)."""
 import io
 import os
 import wave
@@ -103,6 +104,38 @@ def test_host_mirrors_equal_the_numpy_rule(wio, fmt, channels):
         for variant in (0, 1):
             gaps = W.gaps_case(channels, frames, variant)
             assert same_bits(wio.patch_pcm_host(data, wav, fmt, gaps), W.patch_rule(data, wav, fmt, gaps)), ("patch", frames, variant)
+
+
+# ----------------------------------------------------------------------------- 2b. the long clips of the GPU test, on the host
+def test_long_clips_are_past_the_thresholds_their_names_say():
+    tiles = lambda frames: -(-frames // W.T)
+    assert tiles(W.LONG_FRAMES) == W.ENCODE_BLOCKS + 2 and W.LONG_FRAMES - (tiles(W.LONG_FRAMES) - 1) * W.T == 5      # block 1's second tile: 5 frames
+    assert tiles(W.PEAK_FRAMES) == 300 > W.PEAK_THREADS and all(tile < tiles(frames) for frames, tile in W.PEAK_TILES)
+    assert W.LONG_RUN[1] > 3 * W.PATCH_STRIDE and sum(W.LONG_RUN) < W.LONG_FRAMES
+
+
+@pytest.mark.parametrize("fmt,channels", W.LONG_ENCODE)
+def test_host_mirrors_equal_the_numpy_rule_on_a_long_clip(wio, fmt, channels):
+    wav = W.random_wave(channels, W.LONG_FRAMES)
+    data = wio.encode_pcm_host(wav, fmt)
+    assert same_bits(data, W.encode_rule(wav, fmt))
+    assert same_bits(wio.decode_pcm_host(data, fmt, channels), W.decode_rule(data, fmt, channels))
+
+
+@pytest.mark.parametrize("frames,tile", W.PEAK_TILES)
+def test_normalised_host_mirror_finds_the_one_peak_of_a_long_clip(wio, frames, tile):
+    wav = W.peak_clip(frames, tile)
+    got = wio.encode_pcm_host(wav, "s16", normalize=True)
+    assert same_bits(got, W.encode_norm_rule(wav))
+    assert int(got.view("<i2")[tile * W.T + 1]) <= -32766                # the peak is the planted one (the product is truncated): no inf, no nan
+
+
+@pytest.mark.parametrize("fmt,channels", W.LONG_PATCH)
+def test_patch_host_equals_the_numpy_rule_on_a_long_run(wio, fmt, channels):
+    data = W.random_bytes(fmt, channels, W.LONG_FRAMES)
+    wav = W.random_wave(channels, W.LONG_FRAMES, seed=5)
+    gaps = W.long_patch_gaps(channels)
+    assert same_bits(wio.patch_pcm_host(data, wav, fmt, gaps), W.patch_rule(data, wav, fmt, gaps))
 
 
 # ----------------------------------------------------------------------------- 3. round trips

@@ -4,7 +4,14 @@ the tile edge, a tail tile), at other storage offsets, with nothing written outs
 save_wav bytes of tests/golden/wav_io.npz; `patch_pcm` takes `find_gaps`'s tensors as they are; files round-trip; and `repair_file` leaves every
 byte outside the detected gaps' samples as it was; `repair(sample_rate=)` and `repair_file` at 11 025 and 44 100 Hz, through `inpaint_at_rate`, are
 the composition written out pass by pass, bit for bit.  No tolerance anywhere.  The largest clip of the table is 2 T + 17 = 2065 frames, the
-largest of the foreign-rate tests 9000."""
+largest of the foreign-rate tests 9000.
+
+Long clips (section 1b, against the numpy rule; tests/test_wav_io_cpu.py holds the host mirrors to the same rule on the same clips):
+    test_encode_past_the_capped_grid_equals_the_numpy_rule            2048 T + T + 5 = 2 098 181 frames, 2050 tiles on pcm_encode_kernel's 2048
+                                                                      blocks: the `tile += gridDim.x` walk and its trailing barrier
+    test_normalised_encode_finds_the_one_peak_of_a_long_clip          300 and 2050 tiles: the `i += PCM_THREADS` loop over the peak partials,
+                                                                      the peak behind partial 255
+    test_patch_of_a_run_longer_than_the_grid_equals_the_numpy_rule    a run of 3 * 8192 + 77 samples: pcm_patch_kernel's stride of 32 x 256"""
 import os
 import types
 
@@ -105,6 +112,56 @@ def test_nothing_is_written_outside_the_outputs(fmt, channels):
     with np.errstate(all="ignore"):
         assert same_bits(dst[64:64 + frames * fb], W.encode_rule(W.decode_rule(data, fmt, channels), fmt))
     assert bool((dst[:64] == 0xCD).all()) and bool((dst[64 + frames * fb:] == 0xCD).all())
+
+
+# ----------------------------------------------------------------------------- 1b. long clips: the capped grid, the peak partials, a strided run
+@pytest.mark.parametrize("fmt,channels", W.LONG_ENCODE)
+def test_encode_past_the_capped_grid_equals_the_numpy_rule(fmt, channels):
+    """2050 tiles on 2048 blocks: blocks 0 and 1 encode a second tile through the same stage, block 1's is the 5-frame tail.  The C entry point
+    on a stream with guard bytes on both sides, then the Python call, then the decode of those bytes."""
+    from viai_amd import _lib
+    from viai_amd import wav_io as wio
+    lib = _lib.load()
+    frames, fb = W.LONG_FRAMES, channels * W.BYTES[fmt]
+    wav = W.random_wave(channels, frames)
+    want = W.encode_rule(wav, fmt)
+    w = dev(wav)
+    dst = torch.full((64 + frames * fb + 64,), 0xCD, dtype=torch.uint8, device="cuda")
+    _lib.check(lib.viai_pcm_encode(w.data_ptr(), frames, channels, frames, W.FORMATS.index(fmt), 0, dst.data_ptr() + 64, None, None), "encode")
+    torch.cuda.synchronize()
+    assert same_bits(dst[64:64 + frames * fb], want)
+    assert bool((dst[:64] == 0xCD).all()) and bool((dst[64 + frames * fb:] == 0xCD).all())      # no byte behind the stream is written
+    got = wio.encode_pcm(w, fmt)
+    assert same_bits(got, want) and same_bits(w, wav)
+    assert same_bits(wio.decode_pcm(got, fmt, channels), W.decode_rule(want, fmt, channels))
+
+
+@pytest.mark.parametrize("frames,tile", W.PEAK_TILES)
+def test_normalised_encode_finds_the_one_peak_of_a_long_clip(frames, tile):
+    """the peak in a tile whose partial is a thread's first read (0, 255), its second (256), its eighth (2047) and its ninth (2049, the tail)"""
+    from viai_amd import wav_io as wio
+    wav = W.peak_clip(frames, tile)
+    assert same_bits(wio.encode_pcm(dev(wav), "s16", normalize=True), W.encode_norm_rule(wav))
+
+
+@pytest.mark.parametrize("fmt,channels", W.LONG_PATCH)
+def test_patch_of_a_run_longer_than_the_grid_equals_the_numpy_rule(fmt, channels):
+    from viai_amd import wav_io as wio
+    frames, bps = W.LONG_FRAMES, W.BYTES[fmt]
+    data = W.random_bytes(fmt, channels, frames)
+    wav = W.random_wave(channels, frames, seed=5)
+    gaps = W.long_patch_gaps(channels)
+    d = dev(data)
+    got = wio.patch_pcm(d, dev(wav), fmt, tuple(dev(g) for g in gaps))
+    assert same_bits(got, W.patch_rule(data, wav, fmt, gaps)) and same_bits(d, data)
+    inside = np.zeros((frames, channels), dtype=bool)
+    for c in range(channels):
+        for k in range(int(gaps[0][c])):
+            inside[gaps[1][c, k]:gaps[1][c, k] + gaps[2][c, k], c] = True
+    assert int(inside.sum()) == W.LONG_RUN[1] + 33
+    new = got.cpu().numpy().reshape(frames, channels, bps)
+    assert np.array_equal(new[~inside], data.reshape(frames, channels, bps)[~inside])            # every byte outside the runs keeps its value
+    assert np.array_equal(new[inside], W.encode_rule(wav, fmt).reshape(frames, channels, bps)[inside])
 
 
 # ----------------------------------------------------------------------------- 2. the reference's save_wav, on the device

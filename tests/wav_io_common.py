@@ -145,6 +145,44 @@ def gaps_case(channels, frames, variant=0, K=4):
     return count, start, length
 
 
+# ----------------------------------------------------------------------------- long clips
+# pcm_encode_kernel's grid stops at 2048 blocks, so from 2048 T frames on a block walks a second tile: 2050 tiles put blocks 0 and 1 there, block 1
+# on the 5-frame tail.  With normalize every block reads the per-tile peaks 256 at a time: above 256 tiles a thread reads more than one.
+# pcm_patch_kernel lays 32 blocks of 256 along a run: a run longer than 8192 samples is walked in strides.
+ENCODE_BLOCKS, PEAK_THREADS, PATCH_STRIDE = 2048, 256, 32 * 256
+LONG_FRAMES = ENCODE_BLOCKS * T + T + 5
+LONG_ENCODE = (("s16", 2), ("s24", 1), ("u8", 3), ("f32", 2))             # even frame bytes (the swizzled stage), odd, odd, a float format
+PEAK_FRAMES = 299 * T + 5                                                 # 300 tiles: the peaks of tiles 256 .. 299 are a thread's second read
+PEAK_TILES = ((PEAK_FRAMES, 0), (PEAK_FRAMES, 255), (PEAK_FRAMES, 256), (LONG_FRAMES, 2047), (LONG_FRAMES, 2049))
+LONG_PATCH = (("s16", 2), ("s24", 1))
+LONG_RUN = (2000003, 3 * PATCH_STRIDE + 77)
+
+
+def peak_clip(frames, tile):
+    """(1, frames) float32 within +-0.3 with the one peak, -0.9, in `tile` (its second frame) and a larger inf and a nan in two other tiles"""
+    rng = np.random.RandomState(frames % 1000 + tile)
+    x = rng.uniform(-0.3, 0.3, (1, frames)).astype(f32)
+    ntiles = -(-frames // T)
+    x[0, ((tile + 7) % ntiles) * T] = np.inf
+    x[0, ((tile + 130) % ntiles) * T + 3] = np.nan
+    x[0, tile * T + 1] = -0.9
+    return x
+
+
+def long_patch_gaps(channels, K=4):
+    """the long run in the last channel, a short one in channel 0 (mono: both in channel 0), and entries behind count that must not be read"""
+    count = np.zeros(channels, dtype=np.int32)
+    start = np.full((channels, K), 5, dtype=np.int32)
+    length = np.full((channels, K), 9, dtype=np.int32)
+    short = (70001, 33)
+    runs = [[short, LONG_RUN]] if channels == 1 else [[short]] + [[] for _ in range(channels - 2)] + [[LONG_RUN]]
+    for c, r in enumerate(runs):
+        count[c] = len(r)
+        for k, (s, l) in enumerate(r):
+            start[c, k], length[c, k] = s, l
+    return count, start, length
+
+
 def wav_file(fmt, channels, rate, data, extra_before=b"", extra_after=b"", tag=None, extensible=False, data_size=None):
     """the bytes of a RIFF/WAVE file around `data`, written out by hand"""
     bps = BYTES[fmt]
